@@ -8,7 +8,12 @@ A "step" is one pass of the hot path over one batch of synthetic input: one full
 fixture tests/golden/n30_dense.npz (circuit gate tensors are tiny and fixed: "synthetic"
 here means no dataset is read; amplitudes are checked against the fixture's statistics).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given and
+prints the result line.  Everything else -- the result check against the reference and the complex128 truth, the
+per-launch roofline block, the legs of the other BASELINE configs, the slice-sharded series, the CPU baseline, other
+workloads (--workload) and precisions (--precision bf16) -- runs under --full, as the benchmark did before the option.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU over RCCL): the unsliced n30
 contraction cannot be sharded the reference's way (slicing inner bonds would end in an 8 GiB
@@ -25,10 +30,15 @@ slices dealt round-robin to the ranks, ONE all-reduce over RCCL closing the time
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` as a CHILD process, before
 this process has touched the GPU) and exits with their status; launched by torch.distributed.run it is a rank.
 
-Output (rank 0): one line per secondary workload leg as it finishes (`{"leg": ...}`), the full record in
-`bench_detail.json` next to this script (and under gpurun_out/ when that directory exists), and as the LAST stdout line
-ONE compact JSON object (< 1.5 KB: metric, value, roofline, cpu_baseline, one [value, frac, check] triple per leg).
-Exit code 1 when a result check fails (the line is still printed, with "check": "FAILED").
+Output (rank 0): a plain run prints ONE JSON line (metric, value, unit, ms_per_step, ...).  Under --full: one line
+per secondary workload leg as it finishes (`{"leg": ...}`), the full record in `bench_detail.json` next to this
+script, and as the LAST stdout line ONE compact JSON object (< 1.5 KB: metric, value, roofline, cpu_baseline, one
+[value, frac, check] triple per leg); exit code 1 when a result check fails (the line is still printed, with
+"check": "FAILED").
+
+--dump-outputs DIR (rank 0): after the timed steps, what the last timed step returned, as DIR/<name>.npy (complex
+values as [..., 2] real/imaginary pairs in float32, positions in float64).  The n30 result has 2^30 amplitudes: a fixed
+sample of DUMP_SAMPLE of them (seed 0, the same on every run) and the 10 000 at Google's bitstrings.
 """
 import argparse
 import json
@@ -348,12 +358,15 @@ def run_sliced(A, name, dev, world, rank, dist, steps, warmup, per_step, precisi
     t0 = time.perf_counter()
     acc = torch.zeros(shape, dtype=torch.complex64, device=dev)
     base = warmup * per_step
+    last = None
     for k in range(steps):
-        A.accumulate(acc, run(base + k * per_step, per_step))
+        last = run(base + k * per_step, per_step)
+        A.accumulate(acc, last)
     if world > 1:
         dist.all_reduce(torch.view_as_real(acc))   # THE collective of the path: one sum of the accumulators
     barrier()
     dt = time.perf_counter() - t0
+    last = last.clone()   # (it is the runner's accumulator, which the profiled step below reuses)
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -385,7 +398,7 @@ def run_sliced(A, name, dev, world, rank, dist, steps, warmup, per_step, precisi
         if precision != "bf16":   # the contract: 1e-5 of the truth, or no farther from it than 2 x the reference's own complex64 run
             ok = ok and (tl <= LOOSE_TOL or tl <= 2 * rl)
     return {
-        "kernel_times_": kernel_times, "vs_c128_truth": vs_truth, "case_": case,
+        "kernel_times_": kernel_times, "vs_c128_truth": vs_truth, "case_": case, "last_": last, "acc_": acc,
         "workload": f"{what}, tests/golden/{fixture}", "value": value, "unit": "TFLOP/s",
         "ms_per_step": dt / steps * 1e3, "ms_per_slice_per_rank": dt / (steps * per_step) * 1e3,
         "slices_per_rank_per_step": per_step, "slices_timed": n_slices, "flops_per_slice": flops_slice,
@@ -626,6 +639,8 @@ def run_workloads(A, dev, cpu_budget, only=None):
 def bench_sliced(args, A, dev, world, rank, dist):
     res = run_sliced(A, args.workload, dev, world, rank, dist, args.steps, args.warmup, args.slices, args.precision,
                      profile=world == 1)
+    if rank == 0 and args.dump_outputs:   # (the last step's slices of rank 0; the accumulator after the all-reduce)
+        write_outputs(args.dump_outputs, {"amplitudes_last_step": pairs(res["last_"]), "amplitudes_accumulated": pairs(res["acc_"])})
     if rank == 0:
         kt = res.pop("kernel_times_", None)
         res = strip_private(res)
@@ -772,6 +787,35 @@ def write_detail(full):
                 pass
 
 
+DUMP_SAMPLE = 1 << 20        # amplitudes of a larger result that --dump-outputs writes (16 MB with their positions)
+DUMP_LIMIT = 64 << 20        # bytes: all arrays of one --dump-outputs together
+
+
+def pairs(t):
+    """complex tensor -> numpy [..., 2] (real, imaginary) in float32 (complex64) or float64 (complex128)."""
+    return torch.view_as_real(t.detach().resolve_conj()).cpu().numpy()
+
+
+def result_sample(flat, name):
+    """{name: amplitudes, name_index: their positions} of a flat complex result: all of it up to DUMP_SAMPLE elements,
+    else a fixed sample of DUMP_SAMPLE positions drawn with seed 0 (the same positions on every run of the same size)."""
+    n = flat.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+    return {name: pairs(flat[torch.from_numpy(idx).to(flat.device)]), name + "_index": idx.astype(np.float64)}
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy; float32 / float64 only, DUMP_LIMIT bytes in all."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` as a plain command: start the N ranks as a CHILD process (never exec, and before this
     process has initialised the GPU: torch.cuda.device_count() does not), relay their output, exit with their status."""
@@ -818,7 +862,20 @@ def main():
                     help="fp32 (default; the metric's arithmetic) or bf16: complex64 in memory, MFMA operands "
                          "rounded to bfloat16, fp32 accumulation (BASELINE configs[4]'s reduced-precision mode; "
                          "reported as its own metric, checked by state fidelity)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline's timed steps: result checks, roofline, the other workloads' legs, "
+                         "the slice-sharded series, the CPU baseline; needed by --workload, --precision bf16, --detail and "
+                         "--only-workloads")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        for given, opt in ((args.workload != "n30", "--workload"), (args.precision != "fp32", "--precision"),
+                           (args.detail, "--detail"), (args.only_workloads, "--only-workloads")):
+            if given:
+                ap.error(f"{opt} is part of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)   # (nothing above this line has touched the GPU)
@@ -884,6 +941,43 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
+
+    def dump(out):   # --dump-outputs: a sample of this rank's result and, at N = 1, its amplitudes at Google's bitstrings
+        flat = out.reshape(-1)
+        arrays = result_sample(flat, "amplitudes")
+        if world == 1:
+            arrays["amplitudes_at_google"] = pairs(flat[torch.from_numpy(rpos).to(dev)])
+        write_outputs(args.dump_outputs, arrays)
+
+    metric = "contracted TFLOP/s, Sycamore n30 m14 full-amplitude (8 real FLOP per complex MAC)" + (", bf16 operands" if bf16 else "")
+    dtype = "c64 in memory, bf16 MFMA operands, fp32 accumulate" if bf16 else "c64 (fp32 MFMA)"
+    if not args.full:   # a plain run: warm-up, the timed steps, their outputs, the line
+        for _ in range(args.warmup):
+            one_step()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = one_step()
+        barrier()
+        dt = time.perf_counter() - t0
+        if world > 1:
+            t = torch.tensor([dt], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        if rank == 0 and args.dump_outputs:
+            dump(out)
+        del out
+        if rank == 0:
+            print(json.dumps({"metric": metric, "value": sig(args.steps * flops_per_step / dt / 1e12, 6), "unit": "TFLOP/s",
+                              "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                              "ms_per_step": sig(dt / args.steps * 1e3, 6), "higher_is_better": True,
+                              "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": dtype,
+                              "data": "circuit fixture", "config": {"workload": "Sycamore n30 m14 full-amplitude, complex64, "
+                                                                                "no slicing (tests/golden/n30_dense.npz)",
+                                                                    "flops_per_step": flops_per_step}}), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
 
     out = None
     for _ in range(args.warmup):
@@ -971,6 +1065,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     C.profiler = None
+    if rank == 0 and args.dump_outputs:
+        dump(out)
     del out
 
     # the same steps once more WITHOUT the per-launch events (what the 2 events per launch inside the timed region cost)
@@ -1043,12 +1139,11 @@ def main():
             if tj is not None:
                 traffic = tj.get("hbm_bytes_per_launch")
         line = {
-            "metric": "contracted TFLOP/s, Sycamore n30 m14 full-amplitude (8 real FLOP per complex MAC)"
-                      + (", bf16 operands" if bf16 else ""),
+            "metric": metric,
             "value": value, "unit": "TFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if world > 1 else "weak",
             "vs_baseline": None,
-            "dtype": "c64 in memory, bf16 MFMA operands, fp32 accumulate" if bf16 else "c64 (fp32 MFMA)",
+            "dtype": dtype,
             "data": "circuit fixture",
             "config": {"workload": "Sycamore n30 m14 full-amplitude, complex64, no slicing, 180-step scheme "
                                    "(tests/golden/n30_dense.npz)",

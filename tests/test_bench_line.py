@@ -56,3 +56,42 @@ def test_gpus_n_without_enough_devices_is_a_clean_error(capsys):
     rc = bench.launch_ranks(4096)
     out = capsys.readouterr().out.strip().splitlines()
     assert rc == 2 and json.loads(out[-1])["n_gpus"] == 4096
+
+
+def test_dump_outputs_sample_and_format(tmp_path, monkeypatch):
+    """--dump-outputs: complex results as float32 [..., 2] pairs; a result larger than DUMP_SAMPLE is sampled at the
+    same seeded positions on every run; anything but float32 / float64, or more than DUMP_LIMIT bytes, is refused."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    flat = torch.arange(1000, dtype=torch.float32) * (1 + 2j)
+    a, b = bench.result_sample(flat, "amps"), bench.result_sample(flat, "amps")
+    assert np.array_equal(a["amps_index"], b["amps_index"]) and a["amps_index"].dtype == np.float64
+    idx = a["amps_index"].astype(np.int64)
+    assert 0 < len(idx) <= 64 and np.all(np.diff(idx) > 0) and idx[-1] < 1000
+    assert a["amps"].dtype == np.float32 and np.array_equal(a["amps"], np.stack([idx, 2 * idx], 1).astype(np.float32))
+    small = bench.result_sample(flat[:10], "amps")
+    assert np.array_equal(small["amps_index"], np.arange(10))
+    bench.write_outputs(str(tmp_path / "out"), a)
+    assert np.array_equal(np.load(tmp_path / "out" / "amps.npy"), a["amps"])
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "bad"), {"c": np.zeros(4, dtype=np.complex64)})
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100)
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(26, dtype=np.float32)})
+
+
+def test_options_of_the_full_run_need_full(monkeypatch, capsys):
+    """Other workloads, precisions and the per-kernel table belong to --full: without it bench.py stops at the argument
+    check (exit 2, before any GPU work); --steps must be at least 1."""
+    import pytest
+    import bench
+    for argv in (["--workload", "n53"], ["--precision", "bf16"], ["--detail", "x.txt"], ["--only-workloads", "n53"],
+                 ["--steps", "0", "--full"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2, argv
+        assert "error" in capsys.readouterr().err

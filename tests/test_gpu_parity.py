@@ -1288,7 +1288,7 @@ def test_bench_gpus_2_as_a_plain_command():
     """`python bench.py --gpus 2` with no WORLD_SIZE in the environment starts its own two ranks as a child process and relays
     rank 0's compact line (here: gloo, both ranks on cuda:0 through the self-test knobs -- a one-GPU box cannot run RCCL;
     on a multi-GPU node the same command runs backend nccl, test_bench_gpus_2_rccl).  The line must fit the driver's tail."""
-    lines, line = _bench_last_line(["--gpus", "2", "--steps", "1", "--warmup", "1", "--slices", "2"],
+    lines, line = _bench_last_line(["--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--slices", "2"],
                                    {"ARTN_BENCH_BACKEND": "gloo", "ARTN_BENCH_DEVICE": "0"})
     assert len(lines[-1]) < 2000
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["check"] == "ok"
@@ -1299,15 +1299,54 @@ def test_bench_gpus_2_as_a_plain_command():
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="RCCL needs one GPU per rank: this box has fewer than 2")
 def test_bench_gpus_2_rccl():
-    lines, line = _bench_last_line(["--gpus", "2", "--steps", "2", "--warmup", "1"], {})
+    lines, line = _bench_last_line(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1"], {})
     assert len(lines[-1]) < 2000 and line["n_gpus"] == 2 and line["config"]["check"] == "ok"
     assert line["sliced"]["ranks_in_collective"] == 2 and line["sliced"]["backend"] == "nccl" and line["sliced"]["check"] == "ok"
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain run prints one line with the headline's figures and runs nothing else; --dump-outputs writes what the last
+    timed step returned: at Google's 10 000 bitstrings it matches the reference's complex64 run, and the sampled
+    positions are the fixed ones."""
+    lines, line = _bench_last_line(["--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], {})
+    assert len(lines) == 1 and "roofline" not in line and "workloads" not in line and "cpu_baseline" not in line
+    assert line["steps"] == 2 and line["unit"] == "TFLOP/s" and line["higher_is_better"] is True
+    assert line["value"] > 10 and abs(line["value"] * line["ms_per_step"] * 1e9 / line["config"]["flops_per_step"] - 1) < 1e-3
+    arrays = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(arrays) == {"amplitudes", "amplitudes_index", "amplitudes_at_google"}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    case = load_case(os.path.join(GOLDEN, "n30_dense.npz"))
+    at = arrays["amplitudes_at_google"]
+    assert at.dtype == np.float32 and at.shape == (10000, 2)
+    assert amp_rel(at[:, 0] + 1j * at[:, 1], case.arrays["amps_at_google"]) <= 1e-5
+    idx = arrays["amplitudes_index"]
+    want_idx = np.unique(np.random.default_rng(0).integers(0, 2 ** 30, 1 << 20)).astype(np.float64)
+    assert idx.dtype == np.float64 and np.array_equal(idx, want_idx)
+    assert arrays["amplitudes"].dtype == np.float32 and arrays["amplitudes"].shape == (len(idx), 2)
+    assert np.isfinite(arrays["amplitudes"]).all() and np.abs(arrays["amplitudes"]).max() > 0
+
+
+def test_bench_sliced_workload_outputs(tmp_path):
+    """--dump-outputs on a sliced workload: the last timed step's slices and the accumulator of all timed steps.  With one
+    warm-up step of 2 slices and 2 timed steps, the timed steps take Gray-code positions 2..5: slices [3, 2] and [6, 7]."""
+    lines, line = _bench_last_line(["--full", "--workload", "n53", "--slices", "2", "--steps", "2", "--warmup", "1",
+                                    "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], {})
+    assert line["config"]["check"] == "ok"
+    case = load_case(os.path.join(GOLDEN, "n53_m14_sliced.npz"))
+
+    def slices(s):
+        return A.sliced_contraction(case.fresh_tensors(device=DEV), case.scheme, case.slicing_indices, (1,), sparse=True,
+                                    device=DEV, slices=s).cpu().numpy()
+    for name, want in (("amplitudes_last_step", slices([6, 7])), ("amplitudes_accumulated", slices([3, 2, 6, 7]))):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (1, 2), name
+        assert np.abs(got[:, 0] + 1j * got[:, 1] - want).max() <= 1e-5 * np.abs(want).max(), name
 
 
 def test_bench_default_line_is_compact():
     """N = 1: every leg on an earlier line, the LAST line under 2 000 characters with value, roofline and (here skipped)
     cpu_baseline; roofline fractions never above 1."""
-    lines, line = _bench_last_line(["--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {})
+    lines, line = _bench_last_line(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {})
     assert len(lines[-1]) < 2000 and line["n_gpus"] == 1 and line["config"]["check"] == "ok"
     assert 0.3 < line["roofline"]["frac"] <= 1.0 and line["roofline"]["bound"] == "mfma"
     legs = [json.loads(ln) for ln in lines[:-1] if ln.startswith('{"leg"')]

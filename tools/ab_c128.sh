@@ -4,7 +4,7 @@ O=gpurun_out/ab_c128.txt
 : > $O
 for f in ${ARTN_AB_LIST:-1 0 2}; do
   echo "== ARTN_BITS128=$f" >> $O
-  ARTN_BITS128=$f python3 bench.py --no-cpu-baseline --steps 2 --only-workloads n30_c128 2>/dev/null | python3 -c "
+  ARTN_BITS128=$f python3 bench.py --full --no-cpu-baseline --steps 2 --only-workloads n30_c128 2>/dev/null | python3 -c "
 import sys,json
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for k,v in l['workloads'].items():

@@ -4,7 +4,7 @@ O=gpurun_out/ab_deep.txt
 : > $O
 for f in ${ARTN_AB_LIST:-1 0 1 0}; do
   echo "== ARTN_GEMM_DEEP=$f" >> $O
-  ARTN_GEMM_DEEP=$f python3 bench.py --no-cpu-baseline --steps 2 --only-workloads ${ARTN_AB_WORK:-n53m20,n53,rand2} 2>/dev/null | python3 -c "
+  ARTN_GEMM_DEEP=$f python3 bench.py --full --no-cpu-baseline --steps 2 --only-workloads ${ARTN_AB_WORK:-n53m20,n53,rand2} 2>/dev/null | python3 -c "
 import sys,json
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for k,v in l['workloads'].items():

@@ -4,7 +4,7 @@ O=gpurun_out/ab_env.txt
 : > $O
 for f in ${ARTN_AB_LIST}; do
   echo "== ${ARTN_AB_VAR}=$f" >> $O
-  env ${ARTN_AB_VAR}=$f python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 --only-workloads ${ARTN_AB_WORK:-n53m20,n53,rand2} 2>/dev/null | python3 -c "
+  env ${ARTN_AB_VAR}=$f python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --only-workloads ${ARTN_AB_WORK:-n53m20,n53,rand2} 2>/dev/null | python3 -c "
 import sys,json
 for ln in sys.stdin.read().strip().splitlines():
     if not ln.startswith('{\"leg\"'): continue

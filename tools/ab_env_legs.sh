@@ -6,7 +6,7 @@ O=gpurun_out/ab_env_legs_$T.txt
 : > $O
 for f in $L; do
   echo "== $V=$f" >> $O
-  env $V=$f python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --only-workloads $W 2>/dev/null | python3 -c "
+  env $V=$f python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --only-workloads $W 2>/dev/null | python3 -c "
 import sys,json
 for ln in sys.stdin.read().strip().splitlines():
     if not ln.startswith('{'): continue

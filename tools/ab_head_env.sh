@@ -7,7 +7,7 @@ O=gpurun_out/ab_head_env_$T.txt
 for f in ${ARTN_AB_LIST}; do
   echo "== ${ARTN_AB_VAR}=$f" >> $O
   if [ -n "${ARTN_AB_WORK:-}" ]; then W="--only-workloads ${ARTN_AB_WORK}"; else W="--no-workloads"; fi
-  env ${ARTN_AB_VAR}=$f python3 bench.py --no-cpu-baseline --steps 5 --warmup 2 $W --detail gpurun_out/detail_${T}_$f.txt 2>/dev/null | python3 -c "
+  env ${ARTN_AB_VAR}=$f python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2 $W --detail ${O%/*}/detail_${T}_$f.txt 2>/dev/null | python3 -c "
 import sys,json
 for ln in sys.stdin.read().strip().splitlines():
     if not ln.startswith('{'): continue

@@ -7,7 +7,7 @@ for rep in 1 2; do
 for lib in default $L; do
   echo "== $lib" >> $O
   if [ $lib = default ]; then E=""; else E="ARTN_LIB=$lib"; fi
-  env $E python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --only-workloads $W 2>/dev/null | python3 -c "
+  env $E python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --only-workloads $W 2>/dev/null | python3 -c "
 import sys,json
 for ln in sys.stdin.read().strip().splitlines():
     if not ln.startswith('{'): continue

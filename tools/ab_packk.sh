@@ -4,7 +4,7 @@ O=gpurun_out/ab_packk.txt
 : > $O
 for mk in 10 8 7; do
   echo "== ARTN_PACKED_MIN_K=$mk" >> $O
-  ARTN_PACKED_MIN_K=$mk python3 bench.py --no-cpu-baseline --steps 2 --only-workloads n53,n53m20,rand2,rand4,n30_sparse10000 2>/dev/null | python3 -c "
+  ARTN_PACKED_MIN_K=$mk python3 bench.py --full --no-cpu-baseline --steps 2 --only-workloads n53,n53m20,rand2,rand4,n30_sparse10000 2>/dev/null | python3 -c "
 import sys,json
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for k,v in l['workloads'].items():

@@ -40,7 +40,7 @@ def counters(sub):
 sq, fe, wr = counters("pmc_sq"), counters("pmc_fetch"), counters("pmc_write")
 big = lambda per: [d for d in per.values() if d["t1"] - d["t0"] > 1e6]  # launches longer than 1 ms
 md = [f"# rocprofv3 summary, round {R}", "",
-      "Command: `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-workloads` (Sycamore n30 m14 full amplitude, 1 x MI355X).",
+      "Command: `python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-workloads` (Sycamore n30 m14 full amplitude, 1 x MI355X).",
       "Kernel trace and each PMC group were collected in separate rocprofv3 runs.", "",
       "## Kernel time (rocprofv3 --kernel-trace --stats)", "",
       "| kernel | calls | total ms | avg us | % |", "|---|---|---|---|---|"]
