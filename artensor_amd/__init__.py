@@ -40,6 +40,15 @@ from .simulation import (  # noqa: F401
     tensor_network_contraction,
 )
 
+from . import born  # noqa: F401
+from .born import (  # noqa: F401
+    fidelity,
+    linear_xeb,
+    marginal_probabilities,
+    norm2,
+    overlap,
+    sample,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

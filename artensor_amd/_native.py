@@ -11,7 +11,7 @@ import threading
 
 import torch
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 ARTN_MAX_LABELS = 96
 ARTN_PROGRAM_MAX_EXT = 256
 ARTN_C64, ARTN_C128, ARTN_C64_BF16 = 0, 1, 2
@@ -59,6 +59,39 @@ class ArtnStepInfo(ctypes.Structure):
     ]
 
 
+class ArtnBornPlan(ctypes.Structure):
+    _fields_ = [
+        ("block_bits", ctypes.c_int32),
+        ("overlap_grid", ctypes.c_int32),
+        ("n_blocks", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
+MARGINAL_GENERIC, MARGINAL_STREAM = 0, 1
+
+
+class ArtnMarginalDesc(ctypes.Structure):
+    _fields_ = [
+        ("dtype", ctypes.c_int32),
+        ("n_dims", ctypes.c_int32),
+        ("extent", ctypes.c_int64 * ARTN_MAX_LABELS),
+        ("stride", ctypes.c_int64 * ARTN_MAX_LABELS),
+        ("keep", ctypes.c_int32 * ARTN_MAX_LABELS),
+    ]
+
+
+class ArtnMarginalInfo(ctypes.Structure):
+    _fields_ = [
+        ("kernel", ctypes.c_int32),
+        ("chunk_bits", ctypes.c_int32),
+        ("bin_bits", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("workspace_bytes", ctypes.c_int64),
+        ("out_elems", ctypes.c_int64),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -103,6 +136,16 @@ _EXPORTS = {
                                                  ctypes.c_void_p]),
     "artn_absmax_normalize_c128": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                   ctypes.c_void_p]),
+    "artn_born_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ArtnBornPlan)]),
+    "artn_born_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_born_block_sums": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_born_pick": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_marginal_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.POINTER(ArtnMarginalInfo)]),
+    "artn_marginal": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

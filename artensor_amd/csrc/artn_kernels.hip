@@ -4014,4 +4014,11 @@ int artn_absmax_normalize_c128(void *x, int64_t n, double *out_absmax, void *str
 }
 
 } // extern "C"
+// Born statistics (artn_born.hip): a translation unit of its own beside -DARTN_TU_MAIN, which reports errors through this hook;
+// part of this one in the single-translation-unit builds
+#ifdef ARTN_TU_MAIN
+int artn_fail_from_unit(int code, const char *msg) { return fail(code, msg); }
+#else
+#include "artn_born.hip"
+#endif
 #endif // !ARTN_TU_PART

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define ARTN_ABI_VERSION 7
+#define ARTN_ABI_VERSION 8
 #define ARTN_MAX_LABELS 96
 
 /* error codes */
@@ -246,6 +246,71 @@ int artn_absmax_normalize_c128(void *x, int64_t n, double *out_absmax, void *str
  * (the arithmetic of complex128 steps; the roofline of a complex128 run is priced against this measured figure).
  * `scratch4`: 4 bytes of device memory.  Synchronous (runs on the null stream and waits). */
 int artn_probe_mfma_rate(int kind, void *scratch4, double *tflops);
+
+/*
+ * Born statistics of an amplitude array (ABI 8): what a consumer of `TensorNetworkSimulation.contraction` does next.
+ * The reference has no call for any of it; its notebook forms a fidelity with torch expressions
+ * (examples/sycamore.ipynb, cell 7: `(full.conj() @ approx.reshape(-1)).abs() / (full.abs().square().sum().sqrt() * ...)`,
+ * six passes over memory and several temporaries of the size of the state), and the result it would feed them is the
+ * permuted view of artensor/simulation.py:115-116, which the entry points below consume in place: they work on the
+ * memory layout, `a` being the n contiguous elements the view covers.
+ * All of them accumulate in float64, form each complex64 term in float64 (convert, then square), use no floating-point
+ * atomics and give bit-identical results from run to run.  Arrays must be 16-byte aligned; n <= 2^40.
+ */
+typedef struct ArtnBornPlan {
+  int32_t block_bits;      /* blocks of 2^block_bits consecutive elements (10..14)                       */
+  int32_t overlap_grid;    /* workgroups of artn_born_overlap: its workspace holds 4 doubles for each    */
+  int64_t n_blocks;        /* ceil(n / 2^block_bits): length of block_sum[] and prefix[]                 */
+  int64_t workspace_bytes; /* scratch artn_born_overlap wants                                            */
+} ArtnBornPlan;
+/* Host-only: the block size, block count and workspace for n elements of `dtype` (ARTN_C64 / ARTN_C128). */
+int artn_born_plan(int64_t n, int32_t dtype, ArtnBornPlan *plan);
+/* out4 (device) = { Re<a|b>, Im<a|b>, sum|a|^2, sum|b|^2 } with <a|b> = sum conj(a[i]) b[i], in ONE pass over both arrays
+ * (notebook cell 7).  b == NULL or b == a: one array is read, out4 = { |a|^2, 0, |a|^2, |a|^2 }.  Per-workgroup partials go
+ * to `ws`, a second one-workgroup launch adds them in a fixed order. */
+int artn_born_overlap(const void *a, const void *b, int64_t n, int32_t dtype, void *ws, int64_t ws_bytes, double *out4,
+                      void *stream);
+/* block_sum[j] = sum of |a[i]|^2 over block j (n_blocks doubles), and, if `prefix` is not NULL, their inclusive prefix sums:
+ * non-decreasing, and prefix[j] > prefix[j-1] only where block_sum[j] > 0. */
+int artn_born_block_sums(const void *a, int64_t n, int32_t dtype, double *block_sum, double *prefix, void *stream);
+/* Resolves m targets t (device, float64, ASCENDING, in [0, prefix[n_blocks-1]]) against the cumulative distribution of |a|^2:
+ * the block is found by bisection of `prefix`, the block is re-read once for all the targets that fall into it with a
+ * float64 running sum in a fixed order, and out_index[s] is the smallest flat index whose running sum exceeds t[s].  An
+ * element with |a|^2 == 0 is never returned; a target at or beyond the last prefix yields the last non-zero element.
+ * out_prob[s] = |a[out_index[s]]|^2.  (out_index[s] = -1 only if every element is zero.) */
+int artn_born_pick(const void *a, int64_t n, int32_t dtype, const double *prefix, const double *targets, int64_t m,
+                   int64_t *out_index, double *out_prob, void *stream);
+
+/*
+ * out[kept multi-index] = sum over the dropped dimensions of |a|^2 for a DENSE tensor (the strides of its dimensions of
+ * extent > 1 are a permutation of a contiguous layout: exactly the permuted result of artensor/simulation.py:115-116).
+ * `out` is float64, row-major over the kept dimensions in the order they are listed.
+ *   ARTN_MARGINAL_STREAM   power-of-two extents, at least 2^12 elements, at most 2^24 KEPT elements: workgroups stream chunks of
+ *                          2^12 contiguous elements, kept bits inside a chunk index float64 bins in LDS, kept bits above it
+ *                          select a partial row of the workspace; a second launch adds the rows in a fixed order.
+ *                          (Power-of-two extents keeping more than 2^24 elements: ARTN_E_UNSUPPORTED.)
+ *   ARTN_MARGINAL_GENERIC  any other extents (bond dimensions 3, 6 ...): one thread per output element; correct, not fast.
+ */
+#define ARTN_MARGINAL_GENERIC 0
+#define ARTN_MARGINAL_STREAM 1
+typedef struct ArtnMarginalDesc {
+  int32_t dtype;
+  int32_t n_dims; /* <= ARTN_MAX_LABELS */
+  int64_t extent[ARTN_MAX_LABELS];
+  int64_t stride[ARTN_MAX_LABELS]; /* in elements */
+  int32_t keep[ARTN_MAX_LABELS];   /* non-zero: the dimension stays */
+} ArtnMarginalDesc;
+typedef struct ArtnMarginalInfo {
+  int32_t kernel;     /* ARTN_MARGINAL_*                                   */
+  int32_t chunk_bits; /* streaming: log2 elements per chunk                */
+  int32_t bin_bits;   /* streaming: log2 float64 bins in LDS               */
+  int32_t grid;       /* workgroups of the first launch                    */
+  int64_t workspace_bytes;
+  int64_t out_elems;
+} ArtnMarginalInfo;
+/* Host-only: validates the layout (ARTN_E_INVALID when it is not dense), picks the kernel, sizes workspace and output. */
+int artn_marginal_query(const ArtnMarginalDesc *d, ArtnMarginalInfo *info);
+int artn_marginal(const ArtnMarginalDesc *d, const void *a, double *out, void *ws, int64_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
