@@ -6,12 +6,12 @@ LIB := artensor_amd/libartn_hip.so
 
 all: $(LIB)
 
-# thirteen objects from ONE source (see "Translation units" in artn_kernels.hip): `make -j8` builds in about a
+# fourteen objects, twelve of them from ONE source (see "Translation units" in artn_kernels.hip): `make -j8` builds in about a
 # minute and a half instead of four
 SRCS := $(CSRC)/artn_kernels.hip $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/artn_pgemm_kernel.h $(CSRC)/artn_xgemm128_kernel.h \
         $(CSRC)/artn_bits128_kernel.h $(CSRC)/artn_bits3_kernel.h $(CSRC)/artn_wide_kernel.h $(CSRC)/artn_plan.h \
         $(CSRC)/artn_xgemm_plan.h $(CSRC)/artn_xgemm_kernel.h $(CSRC)/artn_xrow_kernel.h $(CSRC)/artn_xgemm_pc_kernel.h include/artn.h \
-        $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h
+        $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h
 OBJDIR := build/obj
 # The product library carries what the default planner can select.  `make dev` (DEV=1) adds the development-only pieces:
 # every ARTN_* planner switch of the A/B measurements in DESIGN.md (-DARTN_DEV_SWITCHES), three-step fusion (artn_k_bits3 /
@@ -26,7 +26,7 @@ DEVOBJS :=
 endif
 # (the longest translation units first: make -j starts its jobs in this order)
 OBJS := $(foreach k,6 5,$(OBJDIR)/bits_k$(k)h0.o $(OBJDIR)/bits_k$(k)h1.o) $(OBJDIR)/main.o $(OBJDIR)/bits_k4.o $(OBJDIR)/bits_k3.o \
-        $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(OBJDIR)/born.o $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
+        $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(OBJDIR)/born.o $(OBJDIR)/rdm.o $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
 FLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Iinclude -I$(CSRC) $(DEVFLAGS)
 
 $(OBJDIR)/main.o: $(SRCS)
@@ -36,6 +36,10 @@ $(OBJDIR)/main.o: $(SRCS)
 $(OBJDIR)/born.o: $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h include/artn.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(FLAGS) -DARTN_TU_BORN -c $< -o $@
+# (reduced density matrices: artn_rdm.hip, likewise)
+$(OBJDIR)/rdm.o: $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h include/artn.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(FLAGS) -DARTN_TU_RDM -c $< -o $@
 $(OBJDIR)/b128.o: $(SRCS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(FLAGS) -DARTN_TU_B128 -c $< -o $@

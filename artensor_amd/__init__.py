@@ -49,6 +49,16 @@ from .born import (  # noqa: F401
     overlap,
     sample,
 )
+from . import rdm  # noqa: F401
+from .rdm import (  # noqa: F401
+    entanglement_entropy,
+    entropy_of,
+    expectation,
+    purity,
+    rdm_info,
+    reduced_density_matrix,
+    renyi_entropy,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

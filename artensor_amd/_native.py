@@ -11,7 +11,7 @@ import threading
 
 import torch
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 ARTN_MAX_LABELS = 96
 ARTN_PROGRAM_MAX_EXT = 256
 ARTN_C64, ARTN_C128, ARTN_C64_BF16 = 0, 1, 2
@@ -92,6 +92,21 @@ class ArtnMarginalInfo(ctypes.Structure):
     ]
 
 
+RDM_GENERIC, RDM_STREAM = 0, 1
+
+
+class ArtnRdmInfo(ctypes.Structure):
+    _fields_ = [
+        ("kernel", ctypes.c_int32),
+        ("panel_bits", ctypes.c_int32),
+        ("tiles", ctypes.c_int32),
+        ("splits", ctypes.c_int32),
+        ("dim", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("flops", ctypes.c_double),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -146,6 +161,10 @@ _EXPORTS = {
     "artn_marginal_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.POINTER(ArtnMarginalInfo)]),
     "artn_marginal": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_int64, ctypes.c_void_p]),
+    "artn_rdm_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.POINTER(ArtnRdmInfo)]),
+    "artn_rdm_row_offsets": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p]),
+    "artn_rdm": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

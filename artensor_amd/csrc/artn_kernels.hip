@@ -4020,5 +4020,6 @@ int artn_absmax_normalize_c128(void *x, int64_t n, double *out_absmax, void *str
 int artn_fail_from_unit(int code, const char *msg) { return fail(code, msg); }
 #else
 #include "artn_born.hip"
+#include "artn_rdm.hip"
 #endif
 #endif // !ARTN_TU_PART

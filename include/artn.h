@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define ARTN_ABI_VERSION 8
+#define ARTN_ABI_VERSION 9
 #define ARTN_MAX_LABELS 96
 
 /* error codes */
@@ -311,6 +311,38 @@ typedef struct ArtnMarginalInfo {
 /* Host-only: validates the layout (ARTN_E_INVALID when it is not dense), picks the kernel, sizes workspace and output. */
 int artn_marginal_query(const ArtnMarginalDesc *d, ArtnMarginalInfo *info);
 int artn_marginal(const ArtnMarginalDesc *d, const void *a, double *out, void *ws, int64_t ws_bytes, void *stream);
+
+/*
+ * Reduced density matrix (ABI 9): out[i][j] = sum_r a[i, r] conj(a[j, r]) for a DENSE tensor, i and j running over the kept
+ * dimensions (in the order they are listed, the first one the most significant digit), r over all the others.  The descriptor
+ * and its checks are those of artn_marginal; the diagonal of the result is what artn_marginal returns.  `out` is D x D
+ * complex128 as interleaved float64 (16-byte aligned), D the product of the kept extents, at most 1024 (more: ARTN_E_UNSUPPORTED).
+ * Unnormalised.  Every product is formed in float64 (complex64 values are converted first), sums are float64 in an order that
+ * depends on the descriptor alone, without floating-point atomics: bit-identical from run to run.  The result is exactly
+ * Hermitian (the lower triangle is computed, the upper one is its conjugate) and the diagonal's imaginary part is exactly 0.
+ *   ARTN_RDM_STREAM   power-of-two extents, at least 2^12 elements, D >= 2 and, where D > 64, at least 16 dropped states:
+ *                     lower-triangle tiles of 64 x 64 (D < 64: one tile of max(D, 16) rows) x `splits` ranges of the dropped
+ *                     index on v_mfma_f64_16x16x4_f64; one partial tile per workgroup in the workspace, a second launch adds
+ *                     them in ascending order.  workspace_bytes = tiles * splits * rows^2 * 16.
+ *   ARTN_RDM_GENERIC  anything else: one workgroup per element of the lower triangle, a fixed tree; correct, not fast.
+ */
+#define ARTN_RDM_GENERIC 0
+#define ARTN_RDM_STREAM 1
+typedef struct ArtnRdmInfo {
+  int32_t kernel;     /* ARTN_RDM_STREAM / ARTN_RDM_GENERIC                             */
+  int32_t panel_bits; /* streaming: log2 columns (dropped states) of a panel in LDS     */
+  int32_t tiles;      /* streaming: lower-triangle tiles                                */
+  int32_t splits;     /* streaming: ranges of the dropped index (partials per element)  */
+  int64_t dim;        /* D                                                              */
+  int64_t workspace_bytes;
+  double flops;       /* real FLOP executed on the matrix cores (0 for the generic form) */
+} ArtnRdmInfo;
+/* Host-only: validates the layout (ARTN_E_INVALID when it is not dense), picks the form, sizes the workspace. */
+int artn_rdm_query(const ArtnMarginalDesc *d, ArtnRdmInfo *info);
+/* Host-only: offset[i] (D entries) = the memory offset, in elements, of the kept digits of row i with every dropped index 0,
+ * read from the same plan tables the kernels use (row i of `out` sums a[offset[i] + r] over the dropped offsets r). */
+int artn_rdm_row_offsets(const ArtnMarginalDesc *d, int64_t *offset);
+int artn_rdm(const ArtnMarginalDesc *d, const void *a, double *out /* [D][D][2] */, void *ws, int64_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
