@@ -6,16 +6,24 @@ LIB := artensor_amd/libartn_hip.so
 
 all: $(LIB)
 
-# fourteen objects, twelve of them from ONE source (see "Translation units" in artn_kernels.hip): `make -j8` builds in about a
-# minute and a half instead of four
-SRCS := $(CSRC)/artn_kernels.hip $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/artn_pgemm_kernel.h $(CSRC)/artn_xgemm128_kernel.h \
-        $(CSRC)/artn_bits128_kernel.h $(CSRC)/artn_bits3_kernel.h $(CSRC)/artn_wide_kernel.h $(CSRC)/artn_plan.h \
-        $(CSRC)/artn_xgemm_plan.h $(CSRC)/artn_xgemm_kernel.h $(CSRC)/artn_xrow_kernel.h $(CSRC)/artn_xgemm_pc_kernel.h include/artn.h \
-        $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h
+# Fourteen objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit),
+# artn_born.hip, artn_rdm.hip, and the eleven few-line sources under units/, each of which defines one artn_launch_*() and so
+# emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by all of them):
+# `make -j8` builds in about a minute and a half instead of four.
+HOST_HDRS := $(CSRC)/artn_host.h include/artn.h
+HDRS := $(HOST_HDRS) $(CSRC)/artn_kernels.hip $(CSRC)/artn_wide_kernel.h $(CSRC)/artn_plan.h $(CSRC)/artn_xgemm_plan.h
+LAUNCH_HDRS := $(CSRC)/artn_launch_bits.h $(CSRC)/artn_launch_bits128.h $(CSRC)/artn_launch_bits3.h \
+               $(CSRC)/artn_bits128_kernel.h $(CSRC)/artn_bits3_kernel.h
+MAIN_HDRS := $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/artn_pgemm_kernel.h $(CSRC)/artn_xgemm_kernel.h \
+             $(CSRC)/artn_xgemm128_kernel.h $(CSRC)/artn_xrow_kernel.h $(CSRC)/artn_xgemm_pc_kernel.h
+BORN_SRCS := $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
+RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(HOST_HDRS)
+# (the single-translation-unit builds below: artn_unity.hip includes every unit source)
+SRCS := $(CSRC)/artn_unity.hip $(CSRC)/artn_api.hip $(wildcard $(CSRC)/units/*.hip) $(HDRS) $(LAUNCH_HDRS) $(MAIN_HDRS) $(BORN_SRCS) $(RDM_SRCS)
 OBJDIR := build/obj
 # The product library carries what the default planner can select.  `make dev` (DEV=1) adds the development-only pieces:
 # every ARTN_* planner switch of the A/B measurements in DESIGN.md (-DARTN_DEV_SWITCHES), three-step fusion (artn_k_bits3 /
-# artn_contract3: -DARTN_DEV_BITS3, three more translation units) and the split-bf16 instantiations (-DARTN_DEV_SPLIT3).
+# artn_contract3: -DARTN_DEV_BITS3, three more units: units/bits3_k*.hip) and the split-bf16 instantiations (-DARTN_DEV_SPLIT3).
 DEV ?= 0
 ifeq ($(DEV),1)
 DEVFLAGS := -DARTN_DEV_SWITCHES -DARTN_DEV_BITS3 -DARTN_DEV_SPLIT3 -DARTN_DEV_XGPC
@@ -29,43 +37,22 @@ OBJS := $(foreach k,6 5,$(OBJDIR)/bits_k$(k)h0.o $(OBJDIR)/bits_k$(k)h1.o) $(OBJ
         $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(OBJDIR)/born.o $(OBJDIR)/rdm.o $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
 FLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Iinclude -I$(CSRC) $(DEVFLAGS)
 
-$(OBJDIR)/main.o: $(SRCS)
+define COMPILE
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_MAIN -c $< -o $@
-# (Born statistics: a source file of its own, artn_born.hip)
-$(OBJDIR)/born.o: $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h include/artn.h
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_BORN -c $< -o $@
-# (reduced density matrices: artn_rdm.hip, likewise)
-$(OBJDIR)/rdm.o: $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h include/artn.h
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_RDM -c $< -o $@
-$(OBJDIR)/b128.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_B128 -c $< -o $@
-$(OBJDIR)/b128a.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_B128A -c $< -o $@
-$(OBJDIR)/wide.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_WIDE -c $< -o $@
-$(OBJDIR)/bits3_k%.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_BITS3=$* -c $< -o $@
-# (the families of 5 and 6 contracted bits in two halves each: second-stage counts 0..3 / 4..6)
-$(OBJDIR)/bits_k%h0.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_BITS=$* -DARTN_TU_HALF=0 -c $< -o $@
-$(OBJDIR)/bits_k%h1.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_BITS=$* -DARTN_TU_HALF=1 -c $< -o $@
-$(OBJDIR)/bits_k%.o: $(SRCS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -DARTN_TU_BITS=$* -c $< -o $@
+	$(HIPCC) $(FLAGS) -c $< -o $@
+endef
+$(OBJDIR)/main.o: $(CSRC)/artn_api.hip $(HDRS) $(MAIN_HDRS)
+	$(COMPILE)
+$(OBJDIR)/born.o: $(BORN_SRCS)
+	$(COMPILE)
+$(OBJDIR)/rdm.o: $(RDM_SRCS)
+	$(COMPILE)
+$(OBJDIR)/%.o: $(CSRC)/units/%.hip $(HDRS) $(LAUNCH_HDRS)
+	$(COMPILE)
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared $(OBJS) -o $@
 
-# the same library from one translation unit (what the diagnostic targets below do with their switches)
+# the same library from one translation unit, artn_unity.hip (what the diagnostic targets below do with their switches)
 single: $(SRCS)
 	$(HIPCC) $(FLAGS) -shared $< -o $(LIB)
 
@@ -103,7 +90,7 @@ ASAN_FLAGS := -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recov
 ASAN_LOG ?= profiles/r06_asan.log
 asan: $(SRCS) tests/csrc/plan_emulate.cpp
 	@mkdir -p $(ASAN_DIR)
-	$(HIPCC) $(ASAN_FLAGS) --offload-host-only -c $(CSRC)/artn_kernels.hip -o $(ASAN_DIR)/host.o
+	$(HIPCC) $(ASAN_FLAGS) --offload-host-only -c $< -o $(ASAN_DIR)/host.o
 	echo "__attribute__((aligned(4096))) const char $$(nm -u $(ASAN_DIR)/host.o | grep -o '__hip_fatbin_[0-9a-f]*' | head -1)[4096] = {0};" > $(ASAN_DIR)/fatbin_stub.c
 	/opt/rocm/lib/llvm/bin/clang -fPIC -c $(ASAN_DIR)/fatbin_stub.c -o $(ASAN_DIR)/fatbin_stub.o
 	$(HIPCC) -fsanitize=address,undefined -shared-libsan -fPIC -shared $(ASAN_DIR)/host.o $(ASAN_DIR)/fatbin_stub.o -o $(ASAN_DIR)/libartn_host_asan.so

@@ -1,4 +1,4 @@
-// artn_bits128_kernel.h -- complex128 state-streaming kernel (included by artn_kernels.hip).
+// artn_bits128_kernel.h -- complex128 state-streaming kernel (included by artn_launch_bits128.h).
 //
 // The reference takes any dtype (`TensorNetworkSimulation.contraction(dtype=...)`,
 // /root/reference/artensor/simulation.py:90).  Until round 3 every complex128 step was one pass of the two-operand GEMM

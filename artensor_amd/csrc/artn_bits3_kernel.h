@@ -1,4 +1,4 @@
-// artn_bits3_kernel.h -- THREE consecutive steps on the state tensor in one pass over HBM (included by artn_kernels.hip).
+// artn_bits3_kernel.h -- THREE consecutive steps on the state tensor in one pass over HBM (included by artn_launch_bits3.h).
 //
 // Reference loop: /root/reference/artensor/contraction.py:66-70 -- `tensors[i] = einsum(eq, tensors[i], tensors[j])` three
 // times on the same tensors[i].  Plan: artn_plan.h make_bits3 (all four tiles 2^12 elements, every result bit of every

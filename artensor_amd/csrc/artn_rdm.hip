@@ -1,25 +1,13 @@
 // artn_rdm.hip -- host half of the reduced-density-matrix entry points of include/artn.h (kernels: artn_rdm_kernel.h).
 //
-// A translation unit of its own in the product build (-DARTN_TU_RDM: build/obj/rdm.o); the single-translation-unit builds
-// (make single / asan / stamps ...) include it at the end of artn_kernels.hip instead, where fail() and HIP_TRY are in scope.
+// A translation unit of its own (build/obj/rdm.o).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "artn.h"
+#include "artn_host.h"
 #include "artn_rdm_kernel.h"
-
-#ifdef ARTN_TU_RDM
-int artn_fail_from_unit(int code, const char *msg); // artn_kernels.hip: sets the thread's artn_last_error()
-static int fail(int code, const std::string &msg) { return artn_fail_from_unit(code, msg.c_str()); }
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(ARTN_E_LAUNCH, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-  } while (0)
-#endif
 
 static int rdm_ceil_log2(int64_t n) {
   int b = 0;

@@ -1,0 +1,22 @@
+// artn_unity.hip -- the whole library as ONE translation unit (make single / stamps / phases / ablate / asan): the
+// __device__ stamp and phase buffers of the diagnostic builds are shared by all kernels, and the sanitizer recipe stands in
+// for exactly one device fat binary.  artn_api.hip comes first: it is the unit that asks artn_kernels.hip for both sections.
+#include "artn_api.hip"
+#include "units/bits_k1.hip"
+#include "units/bits_k2.hip"
+#include "units/bits_k3.hip"
+#include "units/bits_k4.hip"
+#include "units/bits_k5h0.hip"
+#include "units/bits_k5h1.hip"
+#include "units/bits_k6h0.hip"
+#include "units/bits_k6h1.hip"
+#include "units/b128.hip"
+#include "units/b128a.hip"
+#include "units/wide.hip"
+#ifdef ARTN_DEV_BITS3
+#include "units/bits3_k3.hip"
+#include "units/bits3_k4.hip"
+#include "units/bits3_k5.hip"
+#endif
+#include "artn_born.hip"
+#include "artn_rdm.hip"

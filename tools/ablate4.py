@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the n30 pairs whose first stage has 4 contracted bits (development builds with ARTN_DEV_FEW=4)."""
+"""Timing of the n30 pairs whose first stage has 4 contracted bits (any build: they live in units/bits_k4.hip)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic (round 6): how far ahead of their first use does a kernel's ISA issue its LDS reads?
-    hipcc -O3 --offload-arch=gfx950 -Iinclude -Iartensor_amd/csrc -DARTN_TU_BITS=6 -DARTN_TU_HALF=1 --offload-device-only -S \
-          artensor_amd/csrc/artn_kernels.hip -o /tmp/k6h1.s && python3 tools/isa_prefetch_depth.py /tmp/k6h1.s
+    hipcc -O3 --offload-arch=gfx950 -Iinclude -Iartensor_amd/csrc --offload-device-only -S \
+          artensor_amd/csrc/units/bits_k6h1.hip -o /tmp/k6h1.s && python3 tools/isa_prefetch_depth.py /tmp/k6h1.s
 Per artn_k_bits instantiation: MFMA count, and a histogram of "MFMAs issued between a ds_read and the first instruction that
 reads its result" (0 = ds_read, s_waitcnt lgkmcnt(0), use: an exposed LDS round trip; 9 = nine or more).  About 60 zero-distance
 reads are table look-ups outside the stages; a stage whose operand reads are sunk next to their uses shows as 30+ more
