@@ -15,7 +15,8 @@ RuntimeError (the reference prints and sys.exit(1)s, contraction.py:71-74).
 import ctypes
 import threading
 import warnings
-from math import ceil
+from collections import namedtuple
+from math import ceil, prod as _numel
 
 import numpy as np
 import torch
@@ -53,6 +54,22 @@ def _labels(eq):
     """An equation is an einsum string or a triple of label tuples (any hashable labels: no
     50-letter limit, reference contraction.py:9-10)."""
     return _parse(eq) if isinstance(eq, str) else (tuple(eq[0]), tuple(eq[1]), tuple(eq[2]))
+
+
+def _extents(la, lb, shape_a, shape_b, check=False):
+    """label -> extent of one step; check: a label the operands disagree on raises (else the second operand's holds)"""
+    ext = dict(zip(la, shape_a))
+    for lab, n in zip(lb, shape_b):
+        if check and ext.get(lab, n) != n:
+            raise RuntimeError(f"label {lab!r} has extent {ext[lab]} in one operand and {n} in the other")
+        ext[lab] = n
+    return ext
+
+
+def _result_shape(la, lb, lo, shape_a, shape_b, check=False):
+    """Shape of the result `lo` of one step from its labels and operand shapes."""
+    ext = _extents(la, lb, shape_a, shape_b, check)
+    return tuple(ext[x] for x in lo)
 
 
 _DTYPES = {torch.complex64: N.ARTN_C64, torch.complex128: N.ARTN_C128}
@@ -120,10 +137,52 @@ profiler = None
 _info_cache = _IdMemo(8192)    # descriptor -> planner answer
 
 
+def _tic(op=None):
+    """A started (start, end) event pair on the current stream, or None when no profiler is attached.  op: a compiled
+    launch of tensor_contraction -- its planner answer is asked for before the clock starts, not under it."""
+    if profiler is None:
+        return None
+    if op is not None and op.info is None:
+        op.info = _query(op.d1)
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev[0].record()
+    return ev
+
+
+def _toc(ev, info, d=None):
+    """Close a pair of _tic and hand the launch's planner answer to the profiler (info None: the answer for the step
+    descriptor d, looked up after the clock has stopped)."""
+    if ev is not None:
+        ev[1].record()
+        profiler.record(info if info is not None else _step_info_cached(d), ev[0], ev[1])
+
+
+def _info_dict(q):
+    return {name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}
+
+
 def _query(d):
-    info = N.ArtnStepInfo()
-    N.check(N.lib().artn_contract_query(ctypes.byref(d), ctypes.byref(info)))
-    return {name: getattr(info, name) for name, _ in N.ArtnStepInfo._fields_}
+    q = N.ArtnStepInfo()
+    N.check(N.lib().artn_contract_query(ctypes.byref(d), ctypes.byref(q)))
+    return _info_dict(q)
+
+
+def _fused_query(*ds):
+    """The planner's answer for two or three descriptors as ONE launch (artn_contract2_query / artn_contract3_query), or
+    None when it declines to fuse them (status -2); every other failure raises."""
+    q = N.ArtnStepInfo()
+    ask = N.lib().artn_contract2_query if len(ds) == 2 else N.lib().artn_contract3_query
+    rc = ask(*[ctypes.byref(d) for d in ds], ctypes.byref(q))
+    if rc == -2:
+        return None
+    N.check(rc)
+    return _info_dict(q)
+
+
+def _fused_info(memo, ds):
+    """_fused_query remembered per descriptor objects; False: declined"""
+    info = memo.find(ds)
+    return memo.keep(ds, _fused_query(*ds) or False) if info is _MISS else info
 
 
 def _step_info_cached(d):
@@ -195,12 +254,7 @@ def _descriptor(la, lb, lo, a_shape, a_stride, b_shape, b_stride, dtype):
     labels = list(la) + [x for x in lb if x not in la]
     if len(labels) > N.ARTN_MAX_LABELS:
         raise RuntimeError(f"step has {len(labels)} labels; the ABI carries at most {N.ARTN_MAX_LABELS}")
-    ext = {}
-    for lab, n in zip(la, a_shape):
-        ext[lab] = n
-    for lab, n in zip(lb, b_shape):
-        if ext.setdefault(lab, n) != n:
-            raise RuntimeError(f"label {lab!r} has extent {ext[lab]} in one operand and {n} in the other")
+    ext = _extents(la, lb, a_shape, b_shape, check=True)   # (a checking site: the operands must agree on every extent)
     out_shape = tuple(ext[x] for x in lo)
     c_stride = {}
     s = 1
@@ -258,9 +312,7 @@ def _big_k_outer(la, lb, lo, a_shape, a_stride=None, b_shape=None, b_stride=None
     tensors contracted to 2^10 amplitudes); then the slowest-varying contracted labels of A are
     split off until SPLIT_K_MIN_TILES workgroups have work.  Where the planner does not give the
     step to the GEMM kernel the old rule applies: split until MAX_TILE_K_BITS remain."""
-    numel = 1
-    for e in a_shape:
-        numel *= e
+    numel = _numel(a_shape)
     if numel < (1 << 16):
         return None
     if a_stride is None:
@@ -325,9 +377,7 @@ def _big_k_outer_extents(la, lb, lo, a_shape, a_stride, b_shape, b_stride, dtype
     if info["kernel"] != N.KERNEL_XGEMM:
         return None
     tiles = max(1, info["n_tiles"])
-    k_total = 1
-    for _, x in ka:
-        k_total *= a_shape[la.index(x)]
+    k_total = _numel(a_shape[la.index(x)] for _, x in ka)
     outer = []
     for _, x in sorted(ka, reverse=True):   # highest A stride first
         e = a_shape[la.index(x)]
@@ -419,15 +469,13 @@ def contract(eq, a, b, out=None):
     """C = einsum(eq, a, b) on the GPU through artn_contract (stands in for torch.einsum at
     reference contraction.py:70,147,156,163,169,179,181,190).  `eq` is an einsum string or
     a triple of label tuples (labels may then be any hashables: no 50-letter limit)."""
-    la, lb, lo = _parse(eq) if isinstance(eq, str) else (tuple(eq[0]), tuple(eq[1]), tuple(eq[2]))
+    la, lb, lo = _labels(eq)
     N.require_gpu(a, "contract")
     N.require_gpu(b, "contract")
     split = _split_big_k(la, lb, lo, a, b) if a.is_cuda and b.is_cuda and a.dtype == b.dtype else None
     if split is not None:
         (la, lb, lo), a, b, n_outer = split
-        n_rows = 1
-        for e in a.shape[:n_outer]:
-            n_rows *= e
+        n_rows = _numel(a.shape[:n_outer])
         if _sum_leading_ok(a, n_rows):   # the temporary label leads: a plain column sum
             if out is None:
                 return sum_leading(a, n_rows).reshape(a.shape[n_outer:])
@@ -451,15 +499,9 @@ def contract(eq, a, b, out=None):
         return out
     _warn_if_generic(d, max(a.numel(), out.numel()), f"contract({eq!r})" if isinstance(eq, str) else "contract()")
     with torch.cuda.device(a.device):
-        if profiler is None:
-            N.check(_launch_step(d, a, b, out, N.current_stream_ptr(a.device)))
-        else:
-            info = _step_info_cached(d)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            N.check(_launch_step(d, a, b, out, N.current_stream_ptr(a.device)))
-            e1.record()
-            profiler.record(info, e0, e1)
+        ev = _tic()
+        N.check(_launch_step(d, a, b, out, N.current_stream_ptr(a.device)))
+        _toc(ev, None, d)
     return out
 
 
@@ -471,14 +513,22 @@ def _dense_strides(shape):
     return tuple(reversed(st))
 
 
+class _ShapeOnly:
+    """shape / stride / dtype carrier for host-only planner queries"""
+    __slots__ = ("shape", "_st", "dtype")
+
+    def __init__(self, shape, dtype=torch.complex64):
+        self.shape, self._st, self.dtype = tuple(shape), _dense_strides(tuple(shape)), dtype
+
+    def stride(self):
+        return self._st
+
+
 _pair_cache = _IdMemo(4096)     # (descriptor of step 1, of step 2) -> planner answer or False
 
 
 def _resolve_reshape(numel, shape):
-    known = 1
-    for e in shape:
-        if e != -1:
-            known *= e
+    known = _numel(e for e in shape if e != -1)
     if known == 0 or numel % known:
         raise RuntimeError(f"cannot view {numel} elements as {tuple(shape)}")
     return tuple(numel // known if e == -1 else e for e in shape)
@@ -488,15 +538,11 @@ def _pair_descriptors(eq1, a, b1, eq2, b2, mid_view=None):
     """mid_view: the shape the second equation sees the first result in (the free reshape between
     two steps of the sparse executor, reference contraction.py:181); same memory, so only the
     second descriptor's label split changes."""
-    la1, lb1, lo1 = _parse(eq1) if isinstance(eq1, str) else tuple(map(tuple, eq1))
-    la2, lb2, lo2 = _parse(eq2) if isinstance(eq2, str) else tuple(map(tuple, eq2))
+    (la1, lb1, lo1), (la2, lb2, lo2) = _labels(eq1), _labels(eq2)
     d1, mid_shape = _descriptor(la1, lb1, lo1, tuple(a.shape), tuple(a.stride()), tuple(b1.shape),
                                 tuple(b1.stride()), a.dtype)
     if mid_view is not None:
-        numel = 1
-        for e in mid_shape:
-            numel *= e
-        mid_shape = _resolve_reshape(numel, mid_view)
+        mid_shape = _resolve_reshape(_numel(mid_shape), mid_view)
     if len(la2) != len(mid_shape):
         raise RuntimeError("second equation's first operand does not match the first result")
     d2, out_shape = _descriptor(la2, lb2, lo2, mid_shape, _dense_strides(mid_shape), tuple(b2.shape),
@@ -507,9 +553,8 @@ def _pair_descriptors(eq1, a, b1, eq2, b2, mid_view=None):
 def _triple_descriptors(eq1, a, b1, eq2, b2, eq3, b3):
     """Descriptors of three consecutive steps on the same first operand: every later step sees the result before it as
     a dense tensor in that result's label order."""
-    la1, lb1, lo1 = _parse(eq1) if isinstance(eq1, str) else tuple(map(tuple, eq1))
-    la2, lb2, lo2 = _parse(eq2) if isinstance(eq2, str) else tuple(map(tuple, eq2))
-    la3, lb3, lo3 = _parse(eq3) if isinstance(eq3, str) else tuple(map(tuple, eq3))
+    (la1, lb1, lo1), (la2, lb2, lo2) = _labels(eq1), _labels(eq2)
+    la3, lb3, lo3 = _labels(eq3)
     d1, s1 = _descriptor(la1, lb1, lo1, tuple(a.shape), tuple(a.stride()), tuple(b1.shape), tuple(b1.stride()), a.dtype)
     if len(la2) != len(s1):
         raise RuntimeError("second equation's first operand does not match the first result")
@@ -535,70 +580,38 @@ def contract3(eq1, a, b1, eq2, b2, eq3, b3):
         return None
     b1, b2, b3 = _as_operand(b1), _as_operand(b2), _as_operand(b3)
     d1, d2, d3, out_shape = _triple_descriptors(eq1, a, b1, eq2, b2, eq3, b3)
-    info = _triple_cache.find((d1, d2, d3))
-    if info is _MISS:
-        q = N.ArtnStepInfo()
-        rc = N.lib().artn_contract3_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3), ctypes.byref(q))
-        if rc == -2:
-            info = False
-        else:
-            N.check(rc)
-            info = {name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}
-        _triple_cache.keep((d1, d2, d3), info)
+    info = _fused_info(_triple_cache, (d1, d2, d3))
     if info is False:
         return None
     out = torch.empty(out_shape, dtype=a.dtype, device=a.device)
     with torch.cuda.device(a.device):
-        e0 = e1 = None
-        if profiler is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        ev = _tic()
         N.check(N.lib().artn_contract3(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3), a.data_ptr(), b1.data_ptr(),
                                        b2.data_ptr(), b3.data_ptr(), out.data_ptr(), N.current_stream_ptr(a.device)))
-        if profiler is not None:
-            e1.record()
-            profiler.record(info, e0, e1)
+        _toc(ev, info)
     return out
 
 
 def triple_info(eq1, a_shape, b1_shape, eq2, b2_shape, eq3, b3_shape):
     """Planner decision for fusing three consecutive steps (host only); None if the triple does not fit."""
-    class _S:  # shape/stride carrier
-        def __init__(self, shape):
-            self.shape, self._st, self.dtype = tuple(shape), _dense_strides(tuple(shape)), torch.complex64
-
-        def stride(self):
-            return self._st
     if not N.has("artn_contract3_query"):
         return None   # (the product library has no triples: development builds only, make dev)
-    d1, d2, d3, out_shape = _triple_descriptors(eq1, _S(a_shape), _S(b1_shape), eq2, _S(b2_shape), eq3, _S(b3_shape))
-    info = N.ArtnStepInfo()
-    rc = N.lib().artn_contract3_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3), ctypes.byref(info))
-    if rc == -2:
-        return None
-    N.check(rc)
-    res = {name: getattr(info, name) for name, _ in N.ArtnStepInfo._fields_}
-    res["out_shape"] = out_shape
-    return res
+    S = _ShapeOnly
+    d1, d2, d3, out_shape = _triple_descriptors(eq1, S(a_shape), S(b1_shape), eq2, S(b2_shape), eq3, S(b3_shape))
+    info = _fused_query(d1, d2, d3)
+    if info is not None:
+        info["out_shape"] = out_shape
+    return info
 
 
 def pair_info(eq1, a_shape, b1_shape, eq2, b2_shape, dtype=torch.complex64):
     """Planner decision for fusing two consecutive steps (host only); None if not fusable."""
-    class _S:  # shape/stride carrier
-        def __init__(self, shape):
-            self.shape, self._st, self.dtype = tuple(shape), _dense_strides(tuple(shape)), dtype
-
-        def stride(self):
-            return self._st
-    d1, d2, out_shape = _pair_descriptors(eq1, _S(a_shape), _S(b1_shape), eq2, _S(b2_shape))
-    info = N.ArtnStepInfo()
-    rc = N.lib().artn_contract2_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(info))
-    if rc == -2:
-        return None
-    N.check(rc)
-    res = {name: getattr(info, name) for name, _ in N.ArtnStepInfo._fields_}
-    res["out_shape"] = out_shape
-    return res
+    d1, d2, out_shape = _pair_descriptors(eq1, _ShapeOnly(a_shape, dtype), _ShapeOnly(b1_shape, dtype), eq2,
+                                          _ShapeOnly(b2_shape, dtype))
+    info = _fused_query(d1, d2)
+    if info is not None:
+        info["out_shape"] = out_shape
+    return info
 
 
 def contract2(eq1, a, b1, eq2, b2, mid_view=None):
@@ -612,46 +625,24 @@ def contract2(eq1, a, b1, eq2, b2, mid_view=None):
         return None
     b1, b2 = _as_operand(b1), _as_operand(b2)
     d1, d2, out_shape = _pair_descriptors(eq1, a, b1, eq2, b2, mid_view)
-    info = _pair_cache.find((d1, d2))
-    if info is _MISS:
-        q = N.ArtnStepInfo()
-        rc = N.lib().artn_contract2_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(q))
-        if rc == -2:
-            info = False
-        else:
-            N.check(rc)
-            info = {name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}
-        _pair_cache.keep((d1, d2), info)
+    info = _fused_info(_pair_cache, (d1, d2))
     if info is False:
         return None
     out = torch.empty(out_shape, dtype=a.dtype, device=a.device)
     with torch.cuda.device(a.device):
-        e0 = e1 = None
-        if profiler is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        ev = _tic()
         N.check(N.lib().artn_contract2(ctypes.byref(d1), ctypes.byref(d2), a.data_ptr(), b1.data_ptr(),
                                        b2.data_ptr(), out.data_ptr(), N.current_stream_ptr(a.device)))
-        if profiler is not None:
-            e1.record()
-            profiler.record(info, e0, e1)
+        _toc(ev, info)
     return out
 
 
 def step_info(eq, a_shape, b_shape, dtype=torch.complex64, a_stride=None, b_stride=None):
     """Planner decision for one step (host only, works without a GPU)."""
-    la, lb, lo = _parse(eq) if isinstance(eq, str) else (tuple(eq[0]), tuple(eq[1]), tuple(eq[2]))
-
-    def dense(shape):
-        st, s = [], 1
-        for n in reversed(shape):
-            st.append(s)
-            s *= n
-        return tuple(reversed(st))
-
+    la, lb, lo = _labels(eq)
     a_shape, b_shape = tuple(a_shape), tuple(b_shape)
-    d, out_shape = _descriptor(la, lb, lo, a_shape, tuple(a_stride or dense(a_shape)), b_shape,
-                               tuple(b_stride or dense(b_shape)), dtype)
+    d, out_shape = _descriptor(la, lb, lo, a_shape, tuple(a_stride or _dense_strides(a_shape)), b_shape,
+                               tuple(b_stride or _dense_strides(b_shape)), dtype)
     res = dict(_query(d))
     res["out_shape"] = out_shape
     res["note"] = N.lib().artn_last_plan_note().decode()
@@ -777,16 +768,8 @@ def _cut_chain(scheme, members, shapes, dtype, skip):
     seq = [tuple(shapes[i])]
     for n in members:
         (_, j), eq = scheme[n][0], scheme[n][1]
-        la, lb, lo = _labels(eq)
-        ext = dict(zip(la, seq[-1]))
-        ext.update(zip(lb, shapes[j]))
-        seq.append(tuple(ext[x] for x in lo))
-
-    def numel(shape):
-        r = 1
-        for e in shape:
-            r *= e
-        return r
+        seq.append(_result_shape(*_labels(eq), seq[-1], shapes[j]))
+    numel = [_numel(sh) for sh in seq]
     fuse_ok = dtype in _DTYPES
     fuse3_ok = dtype == torch.complex64 and precision.current() in (None, "fp32") and N.has("artn_contract3_query")
     L = len(members)
@@ -799,37 +782,30 @@ def _cut_chain(scheme, members, shapes, dtype, skip):
             return None, None
         return _descriptor(la, lb, lo, shape_in, _dense_strides(shape_in), shapes[j], _dense_strides(shapes[j]), dtype)
     for p in range(L):
-        if not fuse_ok or numel(seq[p]) < FUSE_MIN_NUMEL:
+        if not fuse_ok or numel[p] < FUSE_MIN_NUMEL:
             continue
-        if p + 1 < L and numel(seq[p + 1]) * FUSE_MIN_MID >= numel(seq[p]):
+        if p + 1 < L and numel[p + 1] * FUSE_MIN_MID >= numel[p]:
             d1, mid = desc(p, seq[p])
             d2, out = desc(p + 1, mid) if d1 is not None else (None, None)
             if d2 is not None:
-                q = N.ArtnStepInfo()
-                rc = N.lib().artn_contract2_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(q))
-                if rc == 0:
-                    cand[(p, 2)] = ({name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}, (d1, d2), out)
-                elif rc != -2:
-                    N.check(rc)
+                info = _fused_query(d1, d2)
+                if info is not None:
+                    cand[(p, 2)] = (info, (d1, d2), out)
                 if fuse3_ok and p + 2 < L:
                     d3, out3 = desc(p + 2, out)
-                    if d3 is not None:
-                        q = N.ArtnStepInfo()
-                        rc = N.lib().artn_contract3_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3), ctypes.byref(q))
-                        if rc == 0:
-                            cand[(p, 3)] = ({name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}, (d1, d2, d3), out3)
-                        elif rc != -2:
-                            N.check(rc)
+                    info = _fused_query(d1, d2, d3) if d3 is not None else None
+                    if info is not None:
+                        cand[(p, 3)] = (info, (d1, d2, d3), out3)
     # best[p]: least elements moved for members p..; at equal bytes a pair beats a single step (fewer launches) and a
     # triple must SAVE bytes to be taken (a tiny surcharge: the pair kernels are the measured ones; n30 m14's two fitting
     # triples sit at an odd distance, so they would only trade a pair for a triple and a single step)
     best = [0.0] * (L + 1)
     take = [1] * L
     for p in range(L - 1, -1, -1):
-        best[p], take[p] = numel(seq[p]) + numel(seq[p + 1]) + best[p + 1], 1
+        best[p], take[p] = numel[p] + numel[p + 1] + best[p + 1], 1
         for g in (2, 3):
             if (p, g) in cand:
-                c = numel(seq[p]) + numel(seq[p + g]) + best[p + g] + (1.0 if g == 3 else 0.0)
+                c = numel[p] + numel[p + g] + best[p + g] + (1.0 if g == 3 else 0.0)
                 if c <= best[p]:
                     best[p], take[p] = c, g
     # the cut of rounds 1-3 -- pairs from the left, as fusion_schedule forms them -- stays unless the dynamic programme finds a
@@ -866,6 +842,11 @@ class _Op:
     __slots__ = ("steps", "i", "j", "j2", "j3", "d1", "d2", "d3", "out_shape", "info", "sum_rows", "acc")
     # (acc: False once artn_contract[2]_acc has declined this launch -- see tensor_contraction(accumulate_into=...))
 
+    def __init__(self, steps, i, j, d1, out_shape, j2=None, j3=None, d2=None, d3=None, info=None, sum_rows=0, acc=None):
+        self.steps, self.i, self.j, self.j2, self.j3 = steps, i, j, j2, j3
+        self.d1, self.d2, self.d3, self.out_shape = d1, d2, d3, out_shape
+        self.info, self.sum_rows, self.acc = info, sum_rows, acc
+
 
 
 # ----------------------------------------------------------------------------------------
@@ -900,13 +881,6 @@ def _plan_small_program(scheme, shapes, dtype):
         return None, every
     cur = dict(shapes)
     tainted, main_reads, small, main = set(), set(), [], []
-
-    def numel(sh):
-        n = 1
-        for e in sh:
-            n *= e
-        return n
-
     recs = {}
     for n, step in enumerate(scheme):
         (i, j), eq = step[0], step[1]
@@ -915,10 +889,8 @@ def _plan_small_program(scheme, shapes, dtype):
               and i != j and len(la) == len(cur[i]) and len(lb) == len(cur[j]))
         out_shape = None
         if ok:
-            ext = dict(zip(la, cur[i]))
-            ext.update(zip(lb, cur[j]))
-            out_shape = tuple(ext[x] for x in lo)
-            ok = 0 < max(numel(cur[i]), numel(cur[j]), numel(out_shape)) <= PROGRAM_MAX_NUMEL and numel(out_shape) > 0
+            out_shape = _result_shape(la, lb, lo, cur[i], cur[j])
+            ok = 0 < max(_numel(cur[i]), _numel(cur[j]), _numel(out_shape)) <= PROGRAM_MAX_NUMEL and _numel(out_shape) > 0
         if ok:
             recs[n] = (la, lb, lo, cur[i], cur[j], out_shape)
             small.append(n)
@@ -948,12 +920,6 @@ def _build_program(scheme, small, recs, needed=None, dtype=torch.complex64):
     dtype: complex64 (small matrix-core steps included) or complex128 (artn_k_program<double>: vector ALU only).
     Returns a _Program or None (the caller then runs the steps one by one)."""
     esz = 16 if dtype == torch.complex128 else 8
-    def numel(sh):
-        n = 1
-        for e in sh:
-            n *= e
-        return n
-
     # groups = connected components of the small steps (steps of different groups share no tensor)
     parent = {}
 
@@ -996,7 +962,7 @@ def _build_program(scheme, small, recs, needed=None, dtype=torch.complex64):
         loc[i] = ws
         where[i] = (ws, so)
         step_out[n] = (ws, so)
-        ws += (numel(so) * esz + 15) // 16 * 16
+        ws += (_numel(so) * esz + 15) // 16 * 16
         f = 8.0
         for x in dict.fromkeys(la + lb):
             f *= dict(zip(la, sa)).get(x) or dict(zip(lb, sb))[x]
@@ -1040,23 +1006,18 @@ def _run_program(prog, tensors, dtype, device, stream):
     ext = (ctypes.c_void_p * len(prog.ext_ids))()   # per call: the plan is shared by every thread and device that hits the cache
     for q, t in enumerate(prog.ext_ids):
         ext[q] = tensors[t].data_ptr()
-    if profiler is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _tic()
     N.check(N.lib().artn_program_run(image.data_ptr(), prog.n_groups, ext, len(prog.ext_ids), ws.data_ptr(), _DTYPES[prog.dtype], stream))
-    if profiler is not None:
-        e1.record()
-        profiler.record({"kernel": KERNEL_PROGRAM, "flops": prog.flops, "bytes": 0.0, "k_bits": 0, "k2_bits": 0, "m_tile_bits": 0,
-                         "n_tile_bits": 0, "tile_in_bits": 0, "tile_out_bits": 0, "n_tiles": prog.n_steps, "a_rereads": 1}, e0, e1)
+    if ev is not None:
+        _toc(ev, {"kernel": KERNEL_PROGRAM, "flops": prog.flops, "bytes": 0.0, "k_bits": 0, "k2_bits": 0, "m_tile_bits": 0,
+                  "n_tile_bits": 0, "tile_in_bits": 0, "tile_out_bits": 0, "n_tiles": prog.n_steps, "a_rereads": 1})
     for t, (off, shape) in prog.outputs.items():
         tensors[t] = _ws_view(ws, off, shape, prog.dtype)
     return ws
 
 
 def _ws_view(ws, off, shape, dtype=torch.complex64):
-    n = 16 if dtype == torch.complex128 else 8
-    for e in shape:
-        n *= e
+    n = (16 if dtype == torch.complex128 else 8) * _numel(shape)
     return ws[off:off + n].view(dtype).reshape(shape)
 
 
@@ -1064,6 +1025,52 @@ def _is_plain_step(step):
     """A dense 2-tuple, or a sparse 3-tuple that is not chunked (branch D of the sparse executor, reference
     contraction.py:189-191: its index lists are not looked at): one einsum."""
     return len(step) == 2 or (len(step) == 3 and len(step[2][0]) <= 1)
+
+
+def _dense_groups(scheme, shapes, dtype, in_prog):
+    """First stage of _compile_dense: the steps the small-step program has not taken, in execution order, as one flat list
+    of groups (steps, planner info or None, descriptors or None, result shape or None).  Only the triple cut (_cut_chain)
+    has asked the planner already; a group of two steps without an answer is a CANDIDATE pair.  (Chains and pairs are
+    found on the whole scheme, as if there were no program: steps the program has taken are simply skipped -- they ran
+    before everything else.)  A generator: the second stage emits every group before the next one is formed, so a step
+    that cannot run is reported by the second stage, where it stands in the execution order."""
+    probe = dict(shapes)
+
+    def undecided(steps):
+        steps = tuple(n for n in steps if n not in in_prog)
+        for n in steps:
+            i, j = scheme[n][0]
+            la, lb, lo = _labels(scheme[n][1])
+            if len(la) == len(probe[i]) and len(lb) == len(probe[j]):   # (else: the second stage raises at this step)
+                probe[i] = _result_shape(la, lb, lo, probe[i], probe[j])
+        return [(steps, None, None, None)] if steps else []
+
+    # Three-step fusion (artn_contract3) changes the launch list only where a triple SAVES bytes (section 4.1c of DESIGN.md: on
+    # no committed workload); everywhere else the pairing of rounds 1-3 -- fusion_schedule, pairs from the left -- is kept
+    # exactly: re-pairing alone cost the random D = 2 network 8 % (pairs the old schedule never formed).
+    if (dtype == torch.complex64 and precision.current() in (None, "fp32") and not _os_environ.get("ARTN_NO_FUSE")
+            and N.has("artn_contract3_query")):   # (development builds only: the product library has no triples)
+        groups = []
+        for entry in chain_schedule(scheme):
+            groups += _cut_chain(scheme, entry[1], probe, dtype, in_prog) if entry[0] == "chain" else undecided(entry[1:])
+        if any(len(g[0]) == 3 for g in groups):
+            yield from groups
+            return
+        probe = dict(shapes)
+    if not _chain_plan_on():   # ARTN_CHAIN_PLAN=0: pairs from the left
+        for entry in fusion_schedule(scheme):
+            yield from undecided(entry[1:])
+        return
+    # every chain of steps on one tensor is cut into single steps and candidate pairs by the priced dynamic programme of
+    # the sparse executor (_cut_sparse_chain)
+    for entry in chain_schedule(scheme):
+        members = [n for n in (entry[1] if entry[0] == "chain" else entry[1:]) if n not in in_prog]
+        cut = []
+        if len(members) >= 2:
+            cut = _cut_sparse_chain(scheme, members, tuple(probe[scheme[members[0]][0][0]]),
+                                    [tuple(probe[scheme[n][0][1]]) for n in members], dtype)
+        for g in cut + [(n,) for n in members[sum(map(len, cut)):]]:
+            yield from undecided(g)
 
 
 def _compile_dense(scheme, shapes, dtype):
@@ -1080,19 +1087,12 @@ def _compile_dense(scheme, shapes, dtype):
             shapes[t] = shape
     scheme = _own_layouts(scheme, main_idx, shapes, dtype)
 
-    def emit(n, i, j, la, lb, lo, sa, sb, warn=True):
-        op = _Op()
-        op.steps, op.i, op.j, op.j2, op.d2, op.j3, op.d3 = (n,), i, j, None, None, None, None
-        op.d1, op.out_shape = _descriptor(la, lb, lo, sa, _dense_strides(sa), sb, _dense_strides(sb), dtype)
-        op.info = None
-        op.sum_rows = 0
-        ops.append(op)
-        numel = 1
-        for e in (sa if len(sa) >= len(op.out_shape) else op.out_shape):
-            numel *= e
-        if warn:
-            _warn_if_generic(op.d1, numel, f"tensor_contraction step {n}")
-        return op.out_shape
+    def emit(n, i, j, la, lb, lo, sa, sb, sum_rows=0):
+        d, out_shape = _descriptor(la, lb, lo, sa, _dense_strides(sa), sb, _dense_strides(sb), dtype)
+        ops.append(_Op((n,), i, j, d, out_shape, sum_rows=sum_rows))
+        if j is not _ONE:
+            _warn_if_generic(d, _numel(sa if len(sa) >= len(out_shape) else out_shape), f"tensor_contraction step {n}")
+        return out_shape
 
     def single(n):
         (i, j), eq = scheme[n][0], scheme[n][1]
@@ -1103,135 +1103,37 @@ def _compile_dense(scheme, shapes, dtype):
             # split-K through a temporary batch label, then sum it out (see _split_big_k)
             mid = tuple(outer) + tuple(lo)
             mid_shape = emit(n, i, j, la, lb, mid, shapes[i], shapes[j])
-            shapes[i] = emit(n, i, _ONE, mid, (), lo, mid_shape, (), warn=False)   # runs as artn_sum_axis_c64
-            rows = 1
-            for e in mid_shape[:len(outer)]:
-                rows *= e
-            ops[-1].sum_rows = rows   # the temporary label leads `mid`: a column sum (artn_sum_axis_c64)
+            # (the temporary label leads `mid`: a column sum, artn_sum_axis_c64)
+            shapes[i] = emit(n, i, _ONE, mid, (), lo, mid_shape, (), sum_rows=_numel(mid_shape[:len(outer)]))
         else:
             shapes[i] = emit(n, i, j, la, lb, lo, shapes[i], shapes[j])
 
     def pair(n, m):
-        """steps n and m as one fused launch, if the planner takes them; False: nothing emitted"""
-        (i, j), eq1 = scheme[n][0], scheme[n][1]
-        (_, j2), eq2 = scheme[m][0], scheme[m][1]
-        numel = 1
-        for e in shapes[i]:
-            numel *= e
-        info = None
-        if fuse_ok and numel >= FUSE_MIN_NUMEL:
-            la1, lb1, lo1 = _labels(eq1)
-            la2, lb2, lo2 = _labels(eq2)
-            d1, mid = _descriptor(la1, lb1, lo1, shapes[i], _dense_strides(shapes[i]), shapes[j],
-                                  _dense_strides(shapes[j]), dtype)
-            mid_numel = 1
-            for e in mid:
-                mid_numel *= e
-            if len(la2) == len(mid) and mid_numel * FUSE_MIN_MID >= numel:
-                d2, out_shape = _descriptor(la2, lb2, lo2, mid, _dense_strides(mid), shapes[j2],
-                                            _dense_strides(shapes[j2]), dtype)
-                q = N.ArtnStepInfo()
-                rc = N.lib().artn_contract2_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(q))
-                if rc == 0:
-                    info = {name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}
-                elif rc != -2:
-                    N.check(rc)
-        if info is None:
-            return False
-        op = _Op()
-        op.steps, op.i, op.j, op.j2, op.d1, op.d2, op.out_shape, op.info = (n, m), i, j, j2, d1, d2, out_shape, info
-        op.j3 = op.d3 = None
-        op.sum_rows = 0
-        shapes[i] = out_shape
-        ops.append(op)
-        return True
+        """steps n and m as one fused launch: (planner info, descriptors, result shape), or None if the planner declines"""
+        (i, j), j2 = scheme[n][0], scheme[m][0][1]
+        numel = _numel(shapes[i])
+        if not fuse_ok or numel < FUSE_MIN_NUMEL:
+            return None
+        (la1, lb1, lo1), (la2, lb2, lo2) = _labels(scheme[n][1]), _labels(scheme[m][1])
+        d1, mid = _descriptor(la1, lb1, lo1, shapes[i], _dense_strides(shapes[i]), shapes[j], _dense_strides(shapes[j]), dtype)
+        if len(la2) != len(mid) or _numel(mid) * FUSE_MIN_MID < numel:
+            return None
+        d2, out_shape = _descriptor(la2, lb2, lo2, mid, _dense_strides(mid), shapes[j2], _dense_strides(shapes[j2]), dtype)
+        info = _fused_query(d1, d2)
+        return info and (info, (d1, d2), out_shape)
 
-    # Three-step fusion (artn_contract3) changes the launch list only where a triple SAVES bytes (section 4.1c of DESIGN.md: on
-    # no committed workload); everywhere else the pairing of rounds 1-3 -- fusion_schedule, pairs from the left -- is kept
-    # exactly: re-pairing alone cost the random D = 2 network 8 % (pairs the old schedule never formed).
-    use_chains = False
-    if (dtype == torch.complex64 and precision.current() in (None, "fp32") and not _os_environ.get("ARTN_NO_FUSE")
-            and N.has("artn_contract3_query")):   # (development builds only: the product library has no triples)
-        probe = dict(shapes)
-        for entry in chain_schedule(scheme):
-            if entry[0] == "chain":
-                if any(len(g[0]) == 3 for g in _cut_chain(scheme, entry[1], probe, dtype, in_prog)):
-                    use_chains = True
-                    break
-            elif entry[1] not in in_prog:
-                (ci, cj), ceq = scheme[entry[1]][0], scheme[entry[1]][1]
-                cla, clb, clo = _labels(ceq)
-                cext = dict(zip(cla, probe[ci]))
-                cext.update(zip(clb, probe[cj]))
-                probe[ci] = tuple(cext[x] for x in clo)
-    if use_chains:
-        # (the chains are found on the whole scheme, as if there were no program: steps the program has taken are simply
-        #  skipped -- they ran before everything else)
-        for entry in chain_schedule(scheme):
-            if entry[0] == "one":
-                if entry[1] not in in_prog:
-                    single(entry[1])
-                continue
-            i = scheme[entry[1][0]][0][0]
-            before = dict(shapes)
-            for steps, info, ds, out_shape in _cut_chain(scheme, entry[1], shapes, dtype, in_prog):
-                if len(steps) == 1:
-                    shapes[i] = before[i]
-                    single(steps[0])
-                    before[i] = shapes[i]
-                    continue
-                op = _Op()
-                op.steps, op.i, op.out_shape, op.info, op.sum_rows = steps, i, out_shape, info, 0
-                op.j, op.j2 = scheme[steps[0]][0][1], scheme[steps[1]][0][1]
-                op.j3 = scheme[steps[2]][0][1] if len(steps) == 3 else None
-                op.d1, op.d2 = ds[0], ds[1]
-                op.d3 = ds[2] if len(steps) == 3 else None
-                before[i] = out_shape
-                ops.append(op)
-            shapes[i] = before[i]
-        return prog, ops
-    # (the pairing is decided on the whole scheme, as if there were no program: steps the program has
-    #  taken are simply skipped -- they ran before everything else)
-    if _chain_plan_on():
-        # every chain of steps on one tensor is cut into single steps and fused pairs by the priced dynamic programme of
-        # the sparse executor (_cut_sparse_chain); pairs from the left (fusion_schedule, below) with ARTN_CHAIN_PLAN=0
-        schedule = []
-        for entry in chain_schedule(scheme):
-            if entry[0] == "one":
-                schedule.append(entry)
-                continue
-            members = [n for n in entry[1] if n not in in_prog]
-            if len(members) < 2:
-                schedule += [("one", n) for n in members]
-                continue
-            schedule.append(("cut", members))
-    else:
-        schedule = fusion_schedule(scheme)
-    for entry in schedule:
-        if entry[0] == "one":
-            if entry[1] not in in_prog:
-                single(entry[1])
+    # second stage: one launch per group -- a candidate pair the planner declines after all runs as two single steps
+    for steps, info, ds, out_shape in _dense_groups(scheme, shapes, dtype, in_prog):
+        if info is None and len(steps) == 2:
+            info, ds, out_shape = pair(*steps) or (None, None, None)
+        if info is None:
+            for n in steps:
+                single(n)
             continue
-        if entry[0] == "cut":
-            members = entry[1]
-            ci = scheme[members[0]][0][0]
-            groups = _cut_sparse_chain(scheme, members, tuple(shapes[ci]), [tuple(shapes[scheme[n][0][1]]) for n in members], dtype)
-            covered = sum(len(g) for g in groups)
-            groups += [(n,) for n in members[covered:]]
-            for g in groups:
-                if len(g) == 1 or not pair(g[0], g[1]):
-                    for n in g:
-                        single(n)
-            continue
-        n, m = entry[1], entry[2]
-        if n in in_prog or m in in_prog:
-            for q in (n, m):
-                if q not in in_prog:
-                    single(q)
-            continue
-        if not pair(n, m):
-            single(n)
-            single(m)
+        i = scheme[steps[0]][0][0]
+        j, j2, j3 = ([scheme[n][0][1] for n in steps] + [None])[:3]
+        ops.append(_Op(steps, i, j, ds[0], out_shape, j2=j2, j3=j3, d2=ds[1], d3=ds[2] if len(ds) == 3 else None, info=info))
+        shapes[i] = out_shape
     return prog, ops
 
 
@@ -1398,58 +1300,43 @@ def tensor_contraction(tensors, scheme, accumulate_into=None):
                 continue
             b = _one_scalar(dtype, device) if op.j is _ONE else tensors[op.j]
             fused_acc = False
-            if op is last_op and acc_ok and op.d3 is None and getattr(op, "acc", None) is None:
-                # (decided once per compiled op: a last step that would run packed -- it wants a workspace the accumulating
-                #  entry point does not take -- or has an empty result keeps the separate add)
-                kern = (op.info or _step_info_cached(op.d1))["kernel"] if op.d2 is None else N.KERNEL_BITS_MFMA
-                op.acc = kern == N.KERNEL_BITS_MFMA and accumulate_into.numel() > 0
-            if op is last_op and acc_ok and op.d3 is None and getattr(op, "acc", None) is True:
-                # the slice loop's `collect += result` in the store phase of the last launch
-                if profiler is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                if op.d2 is None:
-                    rc = lib.artn_contract_acc(byref(op.d1), a.data_ptr(), b.data_ptr(), accumulate_into.data_ptr(), stream)
-                else:
-                    rc = lib.artn_contract2_acc(byref(op.d1), byref(op.d2), a.data_ptr(), b.data_ptr(), tensors[op.j2].data_ptr(),
-                                                accumulate_into.data_ptr(), stream)
-                if rc == -2:
-                    op.acc = False   # (this plan's store phase cannot add: remembered per compiled op)
-                else:
-                    fused_acc = True
+            if op is last_op and acc_ok and op.d3 is None and op.acc is not False:
+                if op.acc is None:
+                    # (decided once per compiled op: a last step that would run packed -- it wants a workspace the accumulating
+                    #  entry point does not take -- or has an empty result keeps the separate add)
+                    kern = (op.info or _step_info_cached(op.d1))["kernel"] if op.d2 is None else N.KERNEL_BITS_MFMA
+                    op.acc = kern == N.KERNEL_BITS_MFMA and accumulate_into.numel() > 0
+                if op.acc:
+                    # the slice loop's `collect += result` in the store phase of the last launch
                     out = accumulate_into
-            if fused_acc:
-                pass
-            else:
+                    ev = None if profiler is None else _tic(op)
+                    if op.d2 is None:
+                        rc = lib.artn_contract_acc(byref(op.d1), a.data_ptr(), b.data_ptr(), out.data_ptr(), stream)
+                    else:
+                        rc = lib.artn_contract2_acc(byref(op.d1), byref(op.d2), a.data_ptr(), b.data_ptr(), tensors[op.j2].data_ptr(),
+                                                    out.data_ptr(), stream)
+                    fused_acc = op.acc = rc != -2   # (False: this plan's store phase cannot add -- remembered per compiled op)
+            if not fused_acc:
                 out = torch.empty(op.out_shape, dtype=dtype, device=device)
-                if profiler is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-            if fused_acc:
-                pass
-            elif op.d2 is None:
-                rc = _launch_step(op.d1, a, b, out, stream) if out.numel() else 0
-            elif op.d3 is None:
-                b2 = tensors[op.j2]
-                rc = lib.artn_contract2(byref(op.d1), byref(op.d2), a.data_ptr(), b.data_ptr(), b2.data_ptr(),
-                                        out.data_ptr(), stream)
-            else:
-                b2, b3 = tensors[op.j2], tensors[op.j3]
-                rc = lib.artn_contract3(byref(op.d1), byref(op.d2), byref(op.d3), a.data_ptr(), b.data_ptr(), b2.data_ptr(),
-                                        b3.data_ptr(), out.data_ptr(), stream)
+                ev = None if profiler is None else _tic(op)
+                if op.d2 is None:
+                    rc = _launch_step(op.d1, a, b, out, stream) if out.numel() else 0
+                elif op.d3 is None:
+                    rc = lib.artn_contract2(byref(op.d1), byref(op.d2), a.data_ptr(), b.data_ptr(), tensors[op.j2].data_ptr(),
+                                            out.data_ptr(), stream)
+                else:
+                    rc = lib.artn_contract3(byref(op.d1), byref(op.d2), byref(op.d3), a.data_ptr(), b.data_ptr(),
+                                            tensors[op.j2].data_ptr(), tensors[op.j3].data_ptr(), out.data_ptr(), stream)
             if rc != 0:
                 msg = lib.artn_last_error()
                 raise RuntimeError(f"tensor_contraction failed at step(s) {op.steps} "
                                    f"{[scheme[n][1] for n in op.steps]}: {msg.decode() if msg else rc}")
-            if profiler is not None:
-                e1.record()
-                if op.info is None:
-                    op.info = _query(op.d1)
+            if ev is not None:
                 info = op.info
                 if fused_acc:   # the launch also reads the accumulator
                     info = dict(info)
                     info["bytes"] = info["bytes"] + float(out.numel() * out.element_size())
-                profiler.record(info, e0, e1)
+                _toc(ev, info)
             tensors[op.i] = out
             done_acc = done_acc or fused_acc
     res = tensors[scheme[-1][0][0]]
@@ -1559,10 +1446,7 @@ def _single_row_of_shape(idx, shape, itemsize):
     if v < -rows or v >= rows:
         raise RuntimeError(f"row index out of range: {v} for {rows} rows")
     # (a row of one element would be an 8-byte view: the tiled kernels want 16-byte aligned operands)
-    row_numel = 1
-    for e in shape[1:]:
-        row_numel *= e
-    if rows == 0 or row_numel * itemsize % 16 != 0:
+    if rows == 0 or _numel(shape[1:]) * itemsize % 16 != 0:
         return None
     return v % rows
 
@@ -1587,7 +1471,7 @@ def contract_gathered(eq, a, rows_a, b, rows_b, out=None, label=None, _validate=
     first label of the result (the shared batch label of the sparse executor, reference
     contraction.py:149-156, :177-179).  rows_* are the reference's int64 index tensors or None.
     Returns None when the step does not fit the tiled kernel (the caller gathers instead)."""
-    la, lb, lo = _parse(eq) if isinstance(eq, str) else (tuple(eq[0]), tuple(eq[1]), tuple(eq[2]))
+    la, lb, lo = _labels(eq)
     if a.dtype != b.dtype or a.dtype not in _DTYPES or not lo:
         return None
     lab = lo[0] if label is None else label
@@ -1604,9 +1488,7 @@ def contract_gathered(eq, a, rows_a, b, rows_b, out=None, label=None, _validate=
         part = contract_gathered((la, lb, tuple(outer) + tuple(lo)), a, rows_a, b, rows_b, label=lab, _validate=_validate)
         if part is None:
             return None
-        n_rows = 1
-        for e in part.shape[:len(outer)]:
-            n_rows *= e
+        n_rows = _numel(part.shape[:len(outer)])
         if not _sum_leading_ok(part, n_rows):
             return None
         res = sum_leading(part, n_rows, out=out.reshape(-1) if out is not None and out.is_contiguous() else None)
@@ -1627,10 +1509,7 @@ def contract_gathered(eq, a, rows_a, b, rows_b, out=None, label=None, _validate=
     ib = _device_index(rows_b, b.device, b.shape[0] if _validate else None) if rows_b is not None else None
     flag = _flag(a.device)
     with torch.cuda.device(a.device):
-        e0 = e1 = None
-        if profiler is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        ev = _tic()
         rc = N.lib().artn_contract_gather(ctypes.byref(d), a.data_ptr(), b.data_ptr(), out.data_ptr(), labels.index(lab),
                                           ia.data_ptr() if ia is not None else None, a.shape[0],
                                           ib.data_ptr() if ib is not None else None, b.shape[0],
@@ -1638,9 +1517,7 @@ def contract_gathered(eq, a, rows_a, b, rows_b, out=None, label=None, _validate=
         if rc == -2:
             return None
         N.check(rc)
-        if profiler is not None:
-            e1.record()
-            profiler.record(_step_info_cached(d), e0, e1)
+        _toc(ev, None, d)
     _flags_used().add(a.device)
     return out
 
@@ -1711,7 +1588,7 @@ def contract_row_pairs(eq, a, rows_a, b, rows_b, out=None):
     tiles with 4 valid rows; 2 x 5.4 ms of a 76 ms slice in the reduced-precision mode), as one 2 048 x 512 x 1 024 GEMM plus a
     gather of 64-element rows it is a fraction of a millisecond.  Same products, same sums (fp32 summation order differs).
     Returns None when the pairs do not re-use rows (the caller gathers inside the kernel or materialises the gathers)."""
-    la, lb, lo = _parse(eq) if isinstance(eq, str) else (tuple(eq[0]), tuple(eq[1]), tuple(eq[2]))
+    la, lb, lo = _labels(eq)
     if (rows_a is None or rows_b is None or not la or not lb or not lo or la[0] != lo[0] or lb[0] != lo[0]
             or la[0] in la[1:] or lb[0] in lb[1:] or lo[0] in lo[1:]
             or a.dtype != b.dtype or a.dtype not in _DTYPES or a.dim() != len(la) or b.dim() != len(lb)):
@@ -1741,16 +1618,6 @@ def _normalize_inplace(t):
     with torch.cuda.device(t.device):
         N.check(fn(t.data_ptr(), t.numel(), amax.data_ptr(), N.current_stream_ptr(t.device)))
     return amax
-
-
-def _out_numel(eq, a, b):
-    la, lb, lo = _labels(eq)
-    ext = dict(zip(la, a.shape))
-    ext.update(zip(lb, b.shape))
-    n = 1
-    for x in lo:
-        n *= ext[x]
-    return n
 
 
 def _fusable_kind(step):
@@ -1804,6 +1671,27 @@ def _composed(sel, rows):
     return got
 
 
+def _select_rows(t, idx):
+    """The row select that ends a branch-(C) step: deferred when the tensor is big (see _RowsOf), else gathered now."""
+    if (getattr(_lazy_state, "on", False) and t.numel() >= LAZY_SELECT_MIN_NUMEL and t.dim() > 0
+            and not _is_identity(idx, t.shape[0])):
+        _device_index(idx, t.device, t.shape[0])   # (validated now, as gather_rows would: out of range raises here)
+        return _RowsOf(t, idx)
+    return gather_rows(t, idx)
+
+
+def _finish_sparse_pair(tensors, i, j1, j2, fused, view, select):
+    """The tail of a fused pair of the sparse executor: branch (C) of its second step -- free reshape, optional row select
+    -- then the result replaces tensors[i] and the two consumed operands are released."""
+    if view is not None:
+        fused = fused.reshape(view)
+        if select is not None:
+            fused = _select_rows(fused, select)
+    tensors[i] = fused
+    tensors[j1] = []
+    tensors[j2] = []
+
+
 def _sparse_step(tensors, step):
     """One step of the sparse executor: the four branches of reference contraction.py:140-191."""
     i, j = step[0]
@@ -1828,9 +1716,8 @@ def _sparse_step(tensors, step):
         r0 = 0
         for k in range(len(batch_i)):
             if first is None:
-                ext = dict(zip(la, (rows[k],) + tuple(src_i.shape[1:])))
-                ext.update(zip(lb, (rows[k],) + tuple(src_j.shape[1:])))
-                first = torch.empty((sum(rows),) + tuple(ext[x] for x in lo[1:]), dtype=src_i.dtype, device=src_i.device)
+                tail = _result_shape(la, lb, lo[1:], (rows[k],) + tuple(src_i.shape[1:]), (rows[k],) + tuple(src_j.shape[1:]))
+                first = torch.empty((sum(rows),) + tail, dtype=src_i.dtype, device=src_i.device)
             dst = first[r0:r0 + rows[k]]
             # pairs that re-use few distinct rows: one plain GEMM of the distinct rows + a gather of the pairs; else rows
             # gathered inside the contraction kernel; two gathers + contraction otherwise
@@ -1872,13 +1759,7 @@ def _sparse_step(tensors, step):
     elif len(step) > 3:
         tensors[i] = contract(eq, tensors[i], tensors[j]).reshape(step[3])
         if len(batch_i) == 1:
-            t = tensors[i]
-            if (getattr(_lazy_state, "on", False) and t.numel() >= LAZY_SELECT_MIN_NUMEL and t.dim() > 0
-                    and not _is_identity(batch_i[0], t.shape[0])):
-                _device_index(batch_i[0], t.device, t.shape[0])   # (validated now, as gather_rows would: out of range raises here)
-                tensors[i] = _RowsOf(t, batch_i[0])               # deferred: see _RowsOf
-            else:
-                tensors[i] = gather_rows(t, batch_i[0])
+            tensors[i] = _select_rows(tensors[i], batch_i[0])
         tensors[j] = []
     else:
         tensors[i] = contract(eq, tensors[i], tensors[j])
@@ -1989,22 +1870,15 @@ def _chain_plan_on():
     return _os_environ.get("ARTN_CHAIN_PLAN", "1") not in ("0",)
 
 
-class _ShapeOnly:
-    """shape / stride / dtype carrier for host-only planner queries"""
-    __slots__ = ("shape", "_st", "dtype")
-
-    def __init__(self, shape, dtype):
-        self.shape, self._st, self.dtype = tuple(shape), _dense_strides(tuple(shape)), dtype
-
-    def stride(self):
-        return self._st
+_PlainForm = namedtuple("_PlainForm", "row_a row_b view select a_shape b_shape after view_rows")
 
 
 def _plain_form(step, a_shape, b_shape, itemsize):
-    """How an un-chunked step of the sparse executor runs as ONE plain contraction on (views of) its operands:
-    (row of the first operand or None = all of it, row of the second or None, shape the result is viewed in or None,
-    row select after it or None, shape of tensors[i] afterwards); None for the chunk loop (A) and for gathers of
-    several rows (B with real index lists): those steps are never part of a fused pair."""
+    """How an un-chunked step of the sparse executor runs as ONE plain contraction on (views of) its operands: a _PlainForm
+    (row_a: row of the first operand or None = all of it, row_b: row of the second or None, view: shape the result is
+    viewed in or None, select: row select after it or None, a_shape / b_shape: the operands as the contraction sees them,
+    after: shape of tensors[i] afterwards, view_rows: rows of the view the select picks from); None for the chunk loop (A)
+    and for gathers of several rows (B with real index lists): those steps are never part of a fused pair."""
     bi, bj = step[2] if len(step) > 2 else ((), ())   # (dense steps are 2-tuples: plain contractions)
     if len(bi) > 1:
         return None
@@ -2025,26 +1899,19 @@ def _plain_form(step, a_shape, b_shape, itemsize):
             b_shape = (1,) + tuple(b_shape[1:])
     if len(la) != len(a_shape) or len(lb) != len(b_shape):
         return None
-    ext = dict(zip(la, a_shape))
-    for x, e in zip(lb, b_shape):
-        if ext.setdefault(x, e) != e:
-            return None
-    after = tuple(ext[x] for x in lo)
-    if len(step) > 3 and not (len(bi) == 1 and len(bj) == 1):   # (C): free reshape, optional row select
-        n = 1
-        for e in after:
-            n *= e
-        try:
-            after = _resolve_reshape(n, step[3])
-        except RuntimeError:
-            return None
-        view = step[3]
-        view_rows = after[0] if len(after) else 0
-        if len(bi) == 1:
-            select = bi[0]
-            after = (len(select),) + tuple(after[1:])
-        return ra, rb, view, select, tuple(a_shape), tuple(b_shape), after, view_rows
-    return ra, rb, view, select, tuple(a_shape), tuple(b_shape), after, 0
+    view_rows = 0
+    try:
+        after = _result_shape(la, lb, lo, a_shape, b_shape, check=True)   # (a checking site, as _descriptor)
+        if len(step) > 3 and not (len(bi) == 1 and len(bj) == 1):   # (C): free reshape, optional row select
+            view = step[3]
+            after = _resolve_reshape(_numel(after), view)
+            view_rows = after[0] if len(after) else 0
+            if len(bi) == 1:
+                select = bi[0]
+                after = (len(select),) + tuple(after[1:])
+    except RuntimeError:   # (the operands disagree on an extent, or the view does not fit)
+        return None
+    return _PlainForm(ra, rb, view, select, tuple(a_shape), tuple(b_shape), after, view_rows)
 
 
 _chain_trace = None             # optional hook: called with the prices and the cut of every planned chain
@@ -2099,17 +1966,10 @@ def _cut_sparse_chain(scheme, members, a_shape, b_shapes, dtype):
         if f is None:
             break
         forms.append(f)
-        shape = f[6]
+        shape = f.after
     L = len(forms)
     if L == 0:
         return [(members[0],)]
-
-    def numel(sh):
-        r = 1
-        for e in sh:
-            r *= e
-        return r
-
     single, pair, flops1, pair_q = [0.0] * L, {}, [0.0] * L, {}
     for p in range(L):
         ra, rb, view, select, sa, sb, after, view_rows = forms[p]
@@ -2117,38 +1977,34 @@ def _cut_sparse_chain(scheme, members, a_shape, b_shapes, dtype):
         d, _ = _descriptor(la, lb, lo, sa, _dense_strides(sa), sb, _dense_strides(sb), a.dtype)
         info = _step_info_cached(d)
         single[p], flops1[p] = max(info["bytes"] / CHAIN_BW, info["flops"] / CHAIN_FLOPS), info["flops"]
-        if p + 1 >= L or numel(sa) < FUSE_MIN_NUMEL:
+        if p + 1 >= L or _numel(sa) < FUSE_MIN_NUMEL:
             continue
         # between the two contractions the first step may only reshape (free) or select every row in order (the
         # identity): anything else needs the intermediate in memory; the second step reads ALL of it
-        ra2, sb2 = forms[p + 1][0], forms[p + 1][5]
-        if ra2 is not None or (select is not None and not _is_identity(select, view_rows)):
+        sb2 = forms[p + 1].b_shape
+        if forms[p + 1].row_a is not None or (select is not None and not _is_identity(select, view_rows)):
             continue
-        out1 = numel(after)
-        if out1 * FUSE_MIN_MID < numel(sa):
+        if _numel(after) * FUSE_MIN_MID < _numel(sa):
             continue
         try:
             d1, d2, _ = _pair_descriptors(scheme[members[p]][1], _ShapeOnly(sa, a.dtype), _ShapeOnly(sb, a.dtype),
                                           scheme[members[p + 1]][1], _ShapeOnly(sb2, a.dtype), view)
         except RuntimeError:
             continue
-        q = N.ArtnStepInfo()
-        rc = N.lib().artn_contract2_query(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(q))
-        if rc == -2:
+        q = _fused_query(d1, d2)
+        if q is None:
             continue
-        N.check(rc)
         # a pair's pass costs more per byte than a single step's (two stages per tile between its copy phases: the
         # measured pairs of the n53 slices sit at 1.3-1.4 x bytes / 5 TB/s); a first stage that is re-run for every
         # value of an outer result bit re-reads its input and repeats its FLOP; and the four-wave kernel's instantiations
         # for two 5- or 6-bit stages of which the second SHRINKS the tile spill (6+5: 228 bytes of scratch, 2.05 ms for a
         # pass that two launches do in 0.72 on n53 m14; 5+5: 84 registers, 6.45 ms for 412 GFLOP on the random D = 2 network)
-        rr = max(1, int(q.stage1_reruns))
-        t = max(CHAIN_PAIR_BYTES * (q.bytes + (rr - 1) * float(itemsize) * numel(sa)) / CHAIN_BW,
-                (q.flops + (rr - 1) * flops1[p]) / CHAIN_FLOPS)
-        if q.tile_out_bits < q.tile_mid_bits and q.k_bits >= 5 and q.k2_bits >= 5 and q.grid > 256:
+        rr = max(1, int(q["stage1_reruns"]))
+        t = max(CHAIN_PAIR_BYTES * (q["bytes"] + (rr - 1) * float(itemsize) * _numel(sa)) / CHAIN_BW,
+                (q["flops"] + (rr - 1) * flops1[p]) / CHAIN_FLOPS)
+        if q["tile_out_bits"] < q["tile_mid_bits"] and q["k_bits"] >= 5 and q["k2_bits"] >= 5 and q["grid"] > 256:
             t *= CHAIN_SPILL_FACTOR
-        pair[p] = t
-        pair_q[members[p]] = {name: getattr(q, name) for name, _ in N.ArtnStepInfo._fields_}
+        pair[p], pair_q[members[p]] = t, q
     best, take = [0.0] * (L + 2), [1] * L
     for p in range(L - 1, -1, -1):
         best[p], take[p] = single[p] + best[p + 1], 1
@@ -2168,7 +2024,7 @@ def _cut_sparse_chain(scheme, members, a_shape, b_shapes, dtype):
         groups.append(tuple(members[p:p + g]))
         p += g
     if _chain_trace is not None:   # (tools/chain_plans.py)
-        _chain_trace({"members": list(members[:L]), "log2_numel": [numel(f[4]).bit_length() - 1 for f in forms], "single_ms": [x * 1e3 for x in single],
+        _chain_trace({"members": list(members[:L]), "log2_numel": [_numel(f.a_shape).bit_length() - 1 for f in forms], "single_ms": [x * 1e3 for x in single],
                       "pair_ms": {members[q]: v * 1e3 for q, v in pair.items()}, "cut_ms": best[0] * 1e3, "left_ms": cost_left * 1e3,
                       "groups": groups, "pair_info": pair_q})
     return groups
@@ -2186,35 +2042,24 @@ def _run_sparse_pair(tensors, scheme, n, m):
     if not all(isinstance(t, torch.Tensor) for t in (a, b1, b2)) or not a.is_cuda:
         return False
     f1 = _plain_form(s1, tuple(a.shape), tuple(b1.shape), a.element_size())
-    if f1 is None or (f1[3] is not None and not _is_identity(f1[3], f1[7])):
+    if f1 is None or (f1.select is not None and not _is_identity(f1.select, f1.view_rows)):
         return False
-    f2 = _plain_form(s2, f1[6], tuple(b2.shape), a.element_size())
-    if f2 is None or f2[0] is not None:
+    f2 = _plain_form(s2, f1.after, tuple(b2.shape), a.element_size())
+    if f2 is None or f2.row_a is not None:
         return False
-    if f1[0] is not None:
-        a = a[f1[0]:f1[0] + 1]
-    if f1[1] is not None:
-        b1 = b1[f1[1]:f1[1] + 1]
-    if f2[1] is not None:
-        b2 = b2[f2[1]:f2[1] + 1]
+    if f1.row_a is not None:
+        a = a[f1.row_a:f1.row_a + 1]
+    if f1.row_b is not None:
+        b1 = b1[f1.row_b:f1.row_b + 1]
+    if f2.row_b is not None:
+        b2 = b2[f2.row_b:f2.row_b + 1]
     try:
-        fused = contract2(s1[1], a, b1, s2[1], b2, mid_view=f1[2])
+        fused = contract2(s1[1], a, b1, s2[1], b2, mid_view=f1.view)
     except Exception as e:
         raise RuntimeError(f"tensor_contraction_sparse failed at fused steps {n}+{m}: {e}") from e
     if fused is None:
         return False
-    if f2[2] is not None:   # branch (C) of the second step: free reshape, optional row select
-        fused = fused.reshape(f2[2])
-        if f2[3] is not None:
-            if (getattr(_lazy_state, "on", False) and fused.numel() >= LAZY_SELECT_MIN_NUMEL
-                    and not _is_identity(f2[3], fused.shape[0])):
-                _device_index(f2[3], fused.device, fused.shape[0])
-                fused = _RowsOf(fused, f2[3])
-            else:
-                fused = gather_rows(fused, f2[3])
-    tensors[i] = fused
-    tensors[j1] = []
-    tensors[j2] = []
+    _finish_sparse_pair(tensors, i, j1, j2, fused, f2.view, f2.select)
     return True
 
 
@@ -2242,40 +2087,30 @@ def _run_sparse_main(tensors, scheme, schedule, hoisted, one):
                     one(q)
             continue
         s1, s2 = scheme[n], scheme[m]
+        (i, j1), j2 = s1[0], s2[0][1]
         fused = None
-        for t in (s1[0][1], s2[0][1]):   # (second operands are never read through a deferred select)
+        for t in (j1, j2):   # (second operands are never read through a deferred select)
             if isinstance(tensors[t], _RowsOf):
                 tensors[t] = rows_of(tensors[t])
-        a = tensors[s1[0][0]]
+        a = tensors[i]
         if (_fusable_kind(s1) and _fusable_kind(s2)
                 and isinstance(a, torch.Tensor) and a.is_cuda and a.numel() >= FUSE_MIN_NUMEL
-                and _out_numel(s1[1], a, tensors[s1[0][1]]) * FUSE_MIN_MID >= a.numel()):
+                and (mid_numel := _numel(_result_shape(*_labels(s1[1]), a.shape, tensors[j1].shape))) * FUSE_MIN_MID >= a.numel()):
             # between the two contractions the first step may only reshape (free) or select every
             # row in order (the identity): anything else needs the intermediate in memory
             mid_view = s1[3] if len(s1) > 3 else None
             select1 = s1[2][0][0] if len(s1) > 3 and len(s1[2][0]) == 1 else None
-            rows1 = _resolve_reshape(_out_numel(s1[1], a, tensors[s1[0][1]]), mid_view)[0] if select1 is not None else 0
-            if select1 is None or _is_identity(select1, rows1):
+            if select1 is None or _is_identity(select1, _resolve_reshape(mid_numel, mid_view)[0]):
                 try:
-                    fused = contract2(s1[1], a, tensors[s1[0][1]], s2[1], tensors[s2[0][1]], mid_view=mid_view)
+                    fused = contract2(s1[1], a, tensors[j1], s2[1], tensors[j2], mid_view=mid_view)
                 except Exception as e:
                     raise RuntimeError(f"tensor_contraction_sparse failed at fused steps {n}+{m}: {e}") from e
         if fused is None:
             one(n)
             one(m)
-        else:
-            if len(s2) > 3:  # branch (C) of the second step: free reshape, optional row select
-                fused = fused.reshape(s2[3])
-                if len(s2[2][0]) == 1:
-                    if (getattr(_lazy_state, "on", False) and fused.numel() >= LAZY_SELECT_MIN_NUMEL
-                            and not _is_identity(s2[2][0][0], fused.shape[0])):
-                        _device_index(s2[2][0][0], fused.device, fused.shape[0])
-                        fused = _RowsOf(fused, s2[2][0][0])
-                    else:
-                        fused = gather_rows(fused, s2[2][0][0])
-            tensors[s1[0][0]] = fused
-            tensors[s1[0][1]] = []
-            tensors[s2[0][1]] = []
+        else:   # (branch (C) of the second step: free reshape, optional row select)
+            view2 = s2[3] if len(s2) > 3 else None
+            _finish_sparse_pair(tensors, i, j1, j2, fused, view2, s2[2][0][0] if len(s2[2][0]) == 1 else None)
 
 
 # ----------------------------------------------------------------------------------------

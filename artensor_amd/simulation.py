@@ -15,7 +15,8 @@ import torch
 
 from . import _native as N
 from . import contraction as _C
-from .contraction import _labels, _sparse_step, contract, tensor_contraction, tensor_contraction_sparse
+from .contraction import (_labels, _numel, _resolve_reshape, _result_shape, _sparse_step, contract, tensor_contraction,
+                          tensor_contraction_sparse)
 
 __all__ = ["slice_assignments", "rank_slices", "apply_slice", "accumulate", "sliced_contraction",
            "SliceRunner", "TensorNetworkSimulation", "tensor_network_contraction", "quantum_circuit_simulation",
@@ -214,20 +215,13 @@ def split_scheme(scheme, shapes):
     main_reads = set()   # ids a main step reads as its second operand: a later step that overwrites one
                          # must stay behind that main step (the executors' semantics are sequential)
     small, main = [], []
-
-    def numel(sh):
-        n = 1
-        for e in sh:
-            n *= e
-        return n
-
     for n, step in enumerate(scheme):
         i, j = step[0]
         out_shape = None
         if (i not in tainted and j not in tainted and i not in main_reads and i in shapes and j in shapes
                 and (len(step) == 2 or (len(step[2][0]) <= 1 and len(step[2][1]) <= 1))):
             out_shape = _small_step_shape(step, shapes[i], shapes[j])
-        if out_shape is not None and max(numel(shapes[i]), numel(shapes[j]), numel(out_shape)) <= SMALL_NUMEL:
+        if out_shape is not None and max(_numel(shapes[i]), _numel(shapes[j]), _numel(out_shape)) <= SMALL_NUMEL:
             small.append(n)
             shapes[i] = out_shape
         else:
@@ -250,21 +244,12 @@ def _small_step_shape(step, si, sj):
     la, lb, lo = _labels(step[1])
     if len(la) != len(si) or len(lb) != len(sj):
         return None
-    ext = dict(zip(la, si))
-    ext.update(zip(lb, sj))
-    out = tuple(ext[x] for x in lo)
+    out = _result_shape(la, lb, lo, si, sj)
     if sparse5 and not both:  # branch (C): reshape merges the batch labels, optional row select
-        n = 1
-        for e in out:
-            n *= e
-        rs = list(step[3])
-        known = 1
-        for e in rs:
-            if e != -1:
-                known *= e
-        if known == 0 or n % known:
+        try:
+            out = _resolve_reshape(_numel(out), step[3])
+        except RuntimeError:
             return None
-        out = tuple(n // known if e == -1 else e for e in rs)
         if len(bi) == 1:
             out = (len(bi[0]),) + out[1:]
     return out
@@ -349,12 +334,11 @@ class SliceRunner:
             self._dtype = dtype
             if dtype in (torch.complex64, torch.complex128) and __import__("os").environ.get("ARTN_NO_PROGRAM", "0") in ("", "0"):
                 cur_shapes = dict(shapes)
-                numel = lambda sh: int(np.prod(sh, dtype=np.int64)) if len(sh) else 1
                 for n in small:
                     step = scheme[n]
                     i, j = step[0]
                     out_shape = _small_step_shape(step, cur_shapes[i], cur_shapes[j])
-                    if _C._is_plain_step(step) and 0 < max(numel(cur_shapes[i]), numel(cur_shapes[j]), numel(out_shape)) <= _C.PROGRAM_MAX_NUMEL:
+                    if _C._is_plain_step(step) and 0 < max(_numel(cur_shapes[i]), _numel(cur_shapes[j]), _numel(out_shape)) <= _C.PROGRAM_MAX_NUMEL:
                         la, lb, lo = _labels(step[1])
                         self._recs[n] = (la, lb, lo, tuple(cur_shapes[i]), tuple(cur_shapes[j]), tuple(out_shape))
                     cur_shapes[i] = out_shape
@@ -737,7 +721,6 @@ def partition_output(scheme, leaf_shapes, n_fix):
     in the order of `fixed_dims`, the dims of the original final result they fix (value v of select q
     <-> index v along fixed_dims[q]).  Dims are chosen greedily by how much work fixing them removes
     (labels that join the state early are carried by every big step)."""
-    from .contraction import _labels
     prov = {k: [frozenset([(k, d)]) for d in range(len(sh))] for k, sh in leaf_shapes.items()}
     ext0 = {(k, d): e for k, sh in leaf_shapes.items() for d, e in enumerate(sh)}
     steps = []

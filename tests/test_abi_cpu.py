@@ -173,3 +173,65 @@ def test_single_row_index_lists_follow_the_reference_indexing():
         C._single_row(torch.tensor([3]), t)
     with pytest.raises(RuntimeError, match="row index out of range"):
         C._single_row(torch.tensor([-4]), t)
+
+
+def test_result_shape_is_one_function_with_and_without_the_extent_check():
+    """_result_shape(la, lb, lo, shape_a, shape_b): the shape of a step's result.  The sites that check the two operands'
+    extents against each other (_descriptor, _plain_form) pass check=True and get the descriptor's error; every other site
+    keeps reading the second operand's extent, as its own copy of the computation did."""
+    from artensor_amd import contraction as C
+    la, lb, lo = ("a", "b"), ("b", "c"), ("c", "a")
+    assert C._result_shape(la, lb, lo, (4, 3), (3, 5)) == (5, 4)
+    assert C._result_shape(la, lb, lo, (4, 3), (3, 5), check=True) == (5, 4)
+    assert C._result_shape(la, lb, lo, (4, 3), (2, 5)) == (5, 4)           # (not a checking site: no error)
+    assert C._result_shape(la, lb, ("b",), (4, 3), (2, 5)) == (2,)
+    with pytest.raises(RuntimeError, match="label 'b' has extent 3 in one operand and 2 in the other"):
+        C._result_shape(la, lb, lo, (4, 3), (2, 5), check=True)
+    with pytest.raises(RuntimeError, match="label 'b' has extent 3 in one operand and 2 in the other"):
+        C._descriptor(la, lb, lo, (4, 3), (3, 1), (2, 5), (5, 1), torch.complex64)
+    assert C._plain_form(((0, 1), (la, lb, lo)), (4, 3), (2, 5), 8) is None   # (the chain planner: no form, no error)
+    # empty label tuples: a scalar result, a scalar operand
+    assert C._result_shape(la, la, (), (4, 3), (4, 3), check=True) == ()
+    assert C._result_shape(la, (), la, (4, 3), ()) == (4, 3)
+    assert C._result_shape((), (), (), (), ()) == () and C._numel(()) == 1
+    assert C._numel((4, 3, 0)) == 0 and C._numel((2,) * 40) == 2 ** 40
+
+
+def test_a_compiled_launch_has_defaults_for_everything_but_its_first_step():
+    from artensor_amd import contraction as C
+    d, out_shape = C._descriptor(("a", "b"), ("b", "c"), ("a", "c"), (2, 2), (2, 1), (2, 2), (2, 1), torch.complex64)
+    op = C._Op((0,), 5, 7, d, out_shape)
+    assert (op.steps, op.i, op.j, op.out_shape) == ((0,), 5, 7, (2, 2)) and op.d1 is d
+    assert op.j2 is None and op.j3 is None and op.d2 is None and op.d3 is None and op.info is None
+    assert op.sum_rows == 0 and op.acc is None
+    op = C._Op((0, 1), 5, 7, d, out_shape, j2=8, d2=d, info={"kernel": 1}, sum_rows=4, acc=False)
+    assert (op.j2, op.d2, op.info, op.sum_rows, op.acc) == (8, d, {"kernel": 1}, 4, False)
+    assert not hasattr(op, "__dict__")   # (slots: one of these per launch of every cached plan)
+    # what _compile_dense emits is made of the same thing: the one step of a tiny scheme
+    prog, ops = C._compile_dense([((0, 1), "ab,bc->ac")], {0: (2, 2), 1: (2, 2)}, torch.complex64)
+    assert prog is None and len(ops) == 1
+    op = ops[0]
+    assert (op.steps, op.i, op.j, op.j2, op.j3, op.d2, op.d3, op.info, op.sum_rows, op.acc) == ((0,), 0, 1, None, None, None, None, None, 0, None)
+
+
+@pytest.mark.parametrize("chain_plan", ["1", "0"])
+def test_a_step_whose_equation_does_not_match_its_operand_ranks_is_named_as_such(monkeypatch, chain_plan):
+    """_compile_dense forms the groups of steps before it emits them; a step with more labels than its operand has
+    dimensions must still be refused by the descriptor builder, with its message and at its place in the execution order
+    (not as a label that looks like a missing tensor id)."""
+    from artensor_amd import contraction as C
+    monkeypatch.setenv("ARTN_CHAIN_PLAN", chain_plan)
+    with pytest.raises(RuntimeError, match="operand rank does not match the equation"):
+        C._compile_dense([((0, 1), "abc,bd->acd")], {0: (2, 2), 1: (2, 2)}, torch.complex64)
+    # ... behind good steps on the same tensor, and in front of a step whose operands disagree on an extent: the first
+    # bad step in execution order is the one reported
+    scheme = [((0, 1), "ab,bc->ac"), ((0, 2), "ac,cd->ad"), ((0, 3), "adx,de->ae"), ((0, 4), "ae,ef->af")]
+    shapes = {0: (2, 2), 1: (2, 2), 2: (2, 2), 3: (2, 2), 4: (3, 2)}
+    with pytest.raises(RuntimeError, match="operand rank does not match the equation"):
+        C._compile_dense(scheme, shapes, torch.complex64)
+    scheme[2] = ((0, 3), "ad,de->ae")
+    with pytest.raises(RuntimeError, match="label 'e' has extent 2 in one operand and 3 in the other"):
+        C._compile_dense(scheme, shapes, torch.complex64)
+    with pytest.raises(KeyError):     # (tensor_contraction reports it: "scheme refers to tensor id 7 that was not supplied")
+        C._compile_dense([((0, 7), "ab,bc->ac")], {0: (2, 2)}, torch.complex64)
+

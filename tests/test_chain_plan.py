@@ -50,6 +50,37 @@ def test_plain_form_of_the_four_branches():
     assert f[2] == (-1, 2, 8) and f[3] is sel and f[6] == (3, 2, 8) and f[7] == 8
 
 
+def test_plain_form_fields_are_the_positions_by_name():
+    sel = torch.tensor([0, 2, 5])
+    f = C._plain_form(((0, 1), "ab,cd->acbd", ([sel], []), (-1, 2, 8), None), (4, 2), (2, 8), 8)
+    assert f._fields == ("row_a", "row_b", "view", "select", "a_shape", "b_shape", "after", "view_rows")
+    assert (f.row_a, f.row_b, f.view, f.select, f.a_shape, f.b_shape, f.after, f.view_rows) == tuple(f)
+    assert f.view == f[2] == (-1, 2, 8) and f.select is f[3] is sel and f.after == f[6] == (3, 2, 8) and f.view_rows == f[7] == 8
+    rows = ((0, 1), "ab,ac->abc", ([torch.tensor([3])], [torch.tensor([1])]), None, None)
+    f = C._plain_form(rows, (4, 2), (4, 8), 8)
+    assert (f.row_a, f.row_b) == f[:2] == (3, 1) and f.a_shape == f[4] == (1, 2) and f.b_shape == f[5] == (1, 8)
+    assert f[:4] == (3, 1, None, None) and isinstance(f, tuple) and len(f) == 8
+
+
+def test_a_declined_fused_query_is_none_and_is_remembered_as_false():
+    """The one place that knows the planner's "declined" status: _fused_query gives None for the pair that
+    test_a_declined_pair_does_not_cost_the_next_one builds (k = 8 GEMM step, then k = 3) and the planner's answer for the
+    pair after it; the memo in front of it (contract2's) keeps False for the declined one."""
+    scheme, b_shapes = _chain(26, [(8, 8), (3, 3), (3, 3), (8, 8)])
+    S = C._ShapeOnly
+    d1, d2, _ = C._pair_descriptors(scheme[0][1], S((2,) * 26), S(b_shapes[0]), scheme[1][1], S(b_shapes[1]))
+    assert C._fused_query(d1, d2) is None
+    memo = C._IdMemo(4)
+    assert C._fused_info(memo, (d1, d2)) is False and memo.find((d1, d2)) is False
+    d2b, d3, out_shape = C._pair_descriptors(scheme[1][1], S((2,) * 26), S(b_shapes[1]), scheme[2][1], S(b_shapes[2]))
+    info = C._fused_query(d2b, d3)
+    want = C.pair_info(scheme[1][1], (2,) * 26, b_shapes[1], scheme[2][1], b_shapes[2])
+    assert info is not None and dict(info, out_shape=out_shape) == want
+    assert set(info) == {name for name, _ in A._native.ArtnStepInfo._fields_} and info["k2_bits"] == 3
+    assert C._fused_info(memo, (d2b, d3)) == info and memo.find((d2b, d3)) == info
+    assert C._query(d3) == C._step_info_cached(d3) and C._query(d3)["k_bits"] == 3
+
+
 def test_a_declined_pair_does_not_cost_the_next_one():
     """(k = 8 GEMM step, k = 3) is declined by the planner; pairs from the left then left BOTH steps single and tried the
     third step with the fourth.  The chain cut pairs the second step with the third."""

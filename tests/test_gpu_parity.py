@@ -1754,6 +1754,75 @@ def test_accumulate_in_the_store_phase():
         A.tensor_contraction({0: a.clone(), 1: b}, [((0, 1), "abc,cd->abd")], accumulate_into=acc[:1])
 
 
+class _CountingProfiler:
+    def __init__(self):
+        self.rows = []
+
+    def record(self, info, e0, e1):
+        self.rows.append((info, e0, e1))
+
+
+def _profiled(fn):
+    """fn() without a profiler, then with a counting one attached to contraction.profiler: (plain result, profiled result,
+    the info of every recorded launch).  Every recorded event pair must be a finished, ordered one."""
+    C = A.contraction
+    assert C.profiler is None
+    plain = fn()
+    C.profiler = prof = _CountingProfiler()
+    try:
+        got = fn()
+    finally:
+        C.profiler = None
+    torch.cuda.synchronize()
+    for _, e0, e1 in prof.rows:
+        assert e0.elapsed_time(e1) >= 0.0
+    return plain, got, [info for info, _, _ in prof.rows]
+
+
+def _planned_kernels(scheme, tensors):
+    """what _compile_dense plans for the scheme: the kernel of every launch, the small-step program first"""
+    C = A.contraction
+    prog, ops = C._compile_dense(scheme, {k: tuple(t.shape) for k, t in tensors.items()}, torch.complex64)
+    return ([C.KERNEL_PROGRAM] if prog is not None else []) + [(op.info or C._query(op.d1))["kernel"] for op in ops]
+
+
+def test_the_profiler_counts_the_accumulator_when_the_add_rides_in_the_launch():
+    """tensor_contraction(accumulate_into=...) under contraction.profiler: one record per launch, and the record counts the
+    accumulator's bytes exactly when the add rode in the store phase of the launch (artn_contract_acc).  The big single steps
+    of n30 on the 2^22-element surrogates of test_accumulate_in_the_store_phase, which asserts that the entry point takes at
+    least two of them, and the smoke run's MFMA step (2^20 elements).  Whether it takes a step is asked of the entry point itself."""
+    import ctypes
+    C = A.contraction
+    rng = np.random.default_rng(43)
+    steps = dense_scheme_shapes(load_case(os.path.join(GOLDEN, "n30_dense.npz")))
+    cands = [shrink_step(*steps[n], max_log2=22) for n in (75, 93, 108, 139, 172)]
+    cands.append(("ABCDEFGHIJKLMNOPQRST,DHKOwxyz->ABCEFGIJLMNPQRSTwxyz", (2,) * 20, (2,) * 8))
+    in_launch = 0
+    for eq, a_s, b_s in cands:
+        scheme = [((0, 1), eq)]
+        leaves = {0: gpu(crandn(rng, a_s)), 1: gpu(crandn(rng, b_s))}
+        want = A.step_info(eq, a_s, b_s)
+        assert _planned_kernels(scheme, leaves) == [want["kernel"]]
+        plain, got, infos = _profiled(lambda: A.tensor_contraction(dict(leaves), scheme))
+        assert torch.equal(plain, got) and len(infos) == 1 and infos[0]["kernel"] == want["kernel"] and infos[0]["bytes"] == want["bytes"]
+        acc0 = gpu(crandn(rng, tuple(plain.shape)))
+        d, _ = C._descriptor(*C._labels(eq), tuple(a_s), C._dense_strides(tuple(a_s)), tuple(b_s), C._dense_strides(tuple(b_s)), torch.complex64)
+        rc = -2
+        if want["kernel"] == N.KERNEL_BITS_MFMA:
+            probe = acc0.clone()
+            rc = N.lib().artn_contract_acc(ctypes.byref(d), leaves[0].data_ptr(), leaves[1].data_ptr(), probe.data_ptr(),
+                                           N.current_stream_ptr(torch.device(DEV)))
+            torch.cuda.synchronize()
+            del probe
+        assert rc in (0, -2), N.lib().artn_last_error()
+        plain_acc, got_acc, infos = _profiled(lambda: A.tensor_contraction(dict(leaves), scheme, accumulate_into=acc0.clone()))
+        assert torch.equal(plain_acc, got_acc) and len(infos) == 1 and infos[0]["kernel"] == want["kernel"], eq
+        assert infos[0]["bytes"] == want["bytes"] + (acc0.numel() * 8 if rc == 0 else 0), (eq, rc)
+        assert torch.equal(plain_acc, acc0 + plain), eq     # (one fp32 add per element either way)
+        in_launch += rc == 0
+    assert in_launch >= 2, in_launch
+
+
 @pytest.mark.parametrize("k,nt,ra,seed", [(5, 2, 22, 0), (5, 4, 22, 1), (6, 3, 22, 2), (6, 1, 21, 3), (5, 0, 21, 4), (6, 4, 23, 5), (5, 3, 20, 6)])
 def test_shrinking_single_steps_on_narrow_three_product_blocks(k, nt, ra, seed):
     """ArtnBitsPlan::narrow3 on the GPU (artn_k_bits<KB1, 0, ..., N3>: the 16 x 16 x 4 three-product stage of artn_k_wide on four
@@ -2249,3 +2318,52 @@ def test_step_with_more_labels_than_the_einsum_alphabet():
     many = tuple(f"z{x}" for x in range(97))   # (no tensor library builds a 97-dim tensor: the descriptor builder is asked directly)
     with pytest.raises(RuntimeError, match="at most 96"):
         A.contraction._descriptor(many, (), many, (1,) * 97, (1,) * 97, (), (), torch.complex64)
+
+
+def test_every_entry_point_reports_each_launch_once_to_the_profiler(monkeypatch):
+    """contraction.profiler (bench.py's per-launch timing hook) sees exactly one record per launch from every entry point
+    that launches a contraction, with the planner's answer for THAT launch, and attaching it changes no result bit."""
+    from artensor_amd.contraction import contract2, contract_gathered, pair_info
+    C = A.contraction
+    rng = np.random.default_rng(41)
+    # contract
+    a, b = gpu(crandn(rng, (64, 64))), gpu(crandn(rng, (64, 64)))
+    plain, got, infos = _profiled(lambda: A.contract("ab,bc->ac", a, b))
+    assert torch.equal(plain, got) and len(infos) == 1
+    assert infos[0]["kernel"] == A.step_info("ab,bc->ac", (64, 64), (64, 64))["kernel"]
+    # contract2: the smallest pair of test_random_fused_pairs (2^13 elements)
+    monkeypatch.setenv("ARTN_FORCE_BITS", "1")
+    eq1, eq2 = "ABCDEFGHIJKLM,cdabEAFI->JBdaKbLcDCHGM", "JBdaKbLcDCHGM,bnGB->DJLCanMcdHK"
+    a, b1, b2 = gpu(crandn(rng, (2,) * 13)), gpu(crandn(rng, (2,) * 8)), gpu(crandn(rng, (2,) * 4))
+    want = pair_info(eq1, (2,) * 13, (2,) * 8, eq2, (2,) * 4)
+    plain, got, infos = _profiled(lambda: contract2(eq1, a, b1, eq2, b2))
+    assert want is not None and plain is not None and torch.equal(plain, got) and len(infos) == 1
+    assert infos[0]["kernel"] == want["kernel"] and (infos[0]["k_bits"], infos[0]["k2_bits"]) == (want["k_bits"], want["k2_bits"])
+    monkeypatch.delenv("ARTN_FORCE_BITS")
+    # contract_gathered: the smallest shape of test_contract_gathered
+    na, nb, n, free, kb, nn = 7, 5, 6, 12, 3, 2
+    la = ["z"] + [chr(65 + x) for x in range(free + kb)]
+    kl, nl = la[1:1 + kb], [chr(97 + x) for x in range(nn)]
+    lb, lo = ["z"] + kl[::-1] + nl, ["z"] + [x for x in la[1:] if x not in kl] + nl
+    eq = "".join(la) + "," + "".join(lb) + "->" + "".join(lo)
+    a, b = gpu(crandn(rng, (na,) + (2,) * (len(la) - 1))), gpu(crandn(rng, (nb,) + (2,) * (len(lb) - 1)))
+    ra, rb = torch.from_numpy(rng.integers(0, na, size=n)), torch.from_numpy(rng.integers(0, nb, size=n))
+    plain, got, infos = _profiled(lambda: contract_gathered(eq, a, ra, b, rb))
+    assert plain is not None and torch.equal(plain, got) and len(infos) == 1
+    want = A.step_info(eq, (n,) + tuple(a.shape[1:]), (n,) + tuple(b.shape[1:]), a_stride=a.stride(), b_stride=b.stride())
+    assert infos[0]["kernel"] == want["kernel"]
+    C.check_gather_flag()
+    # tensor_contraction on n12 (one launch: the small-step program), then every step as its own launch, each with and
+    # without accumulate_into
+    for no_program in ("0", "1"):
+        monkeypatch.setenv("ARTN_NO_PROGRAM", no_program)
+        case = load_case(os.path.join(GOLDEN, "n12_dense.npz"))   # (a fresh scheme object: compiled under this setting)
+        leaves = case.fresh_tensors(device=DEV)
+        kernels = _planned_kernels(case.scheme, leaves)
+        assert len(kernels) == (1 if no_program == "0" else len(case.scheme))
+        plain, got, infos = _profiled(lambda: A.tensor_contraction(dict(leaves), case.scheme))
+        assert torch.equal(plain, got) and [info["kernel"] for info in infos] == kernels
+        run_acc = lambda: A.tensor_contraction(dict(leaves), case.scheme, accumulate_into=torch.zeros_like(plain))
+        plain_acc, got_acc, infos = _profiled(run_acc)
+        assert torch.equal(plain_acc, got_acc) and torch.equal(plain_acc, plain) and [info["kernel"] for info in infos] == kernels
+    monkeypatch.delenv("ARTN_NO_PROGRAM")
