@@ -1766,7 +1766,7 @@ def _sparse_step(tensors, step):
         tensors[j] = []
 
 
-_sparse_prog_cache = _IdMemo(64)   # scheme -> (shape signature, program or None, hoisted step indices)
+_sparse_prog_cache = _IdMemo(64)   # scheme -> (dtype + shape signature, program or None, hoisted step indices)
 _NO_HOIST = frozenset()
 
 
@@ -1783,7 +1783,7 @@ def _sparse_program(scheme, tensors):
             on_gpu = on_gpu and t.is_cuda and t.is_contiguous()
     if dtype not in _DTYPES or not on_gpu:
         return None, _NO_HOIST
-    sig = tuple(shapes.items())
+    sig = (dtype,) + tuple(shapes.items())   # (a scheme run in complex64, then in complex128: not the complex64 program)
     hit = _sparse_prog_cache.find((scheme,), schemes=(scheme,))
     if hit is _MISS or hit[0] != sig:
         prog, main = _plan_small_program(scheme, shapes, dtype)
@@ -1793,6 +1793,21 @@ def _sparse_program(scheme, tensors):
 
 
 _defer = threading.local()   # .flag_check: the slice loop reads the gather flag once, after its last slice
+
+
+def _check_chunks(scheme):
+    """Refuse a scheme with a chunked step (branch A) whose chunk lists do not hold as many rows as the step's
+    next_shape says its result has.  The reference's compiler emits such steps whenever a step has fewer rows than about
+    the square of its chunk count (contraction_scheme_sparse, chunking="reference"); its executor then dies with an
+    IndexError at the next step that indexes the short result, or -- when the step is the last -- returns fewer amplitudes
+    than bitstrings.  Checked once per scheme object, before anything is launched."""
+    for n, step in enumerate(scheme):
+        if len(step) > 4 and step[4] and len(step[2][0]) > 1:
+            held = sum(len(x) for x in step[2][0])
+            if held != step[4][0]:
+                raise RuntimeError(f"tensor_contraction_sparse: the {len(step[2][0])} chunks of step {n} {step[0]} hold {held} of the "
+                                   f"step's {step[4][0]} rows (the reference's chunk split leaves rows out when a step has fewer "
+                                   "rows than about the square of its chunk count; compile with chunking='cover')")
 
 
 def tensor_contraction_sparse(tensors, contraction_scheme, scientific_notation=False):
@@ -1813,6 +1828,7 @@ def tensor_contraction_sparse(tensors, contraction_scheme, scientific_notation=F
     scheme = contraction_scheme
     schedule = _schedule_cache.find((scheme,), (_chain_plan_on(),), (scheme,))
     if schedule is _MISS:
+        _check_chunks(scheme)
         schedule = _schedule_cache.keep((scheme,), chain_schedule(scheme) if _chain_plan_on() else fusion_schedule(scheme),
                                         (_chain_plan_on(),), (scheme,))
     factor = None
@@ -2222,7 +2238,7 @@ def _first_index(haystack, needles):
     return order[pos]
 
 
-def contraction_scheme_sparse(ctree, bitstrings=None, sc_target=31, labels="einsum"):
+def contraction_scheme_sparse(ctree, bitstrings=None, sc_target=31, labels="einsum", chunking="reference"):
     """Sparse-state scheme (reference contraction.py:208-341).
 
     Walks the tree's DFS order keeping, per live tensor, which final qubits it already
@@ -2231,7 +2247,17 @@ def contraction_scheme_sparse(ctree, bitstrings=None, sc_target=31, labels="eins
         (edge, eq, batch_seq, rshape_or_None, next_shape)       5-tuple
     with batch labels -1 (left rows), -2 (right rows), -3 (shared rows of a chunked
     gather), exactly the reference's step format.  Returns (scheme, bonds of the final
-    tensor, bitstrings in output-row order)."""
+    tensor, bitstrings in output-row order).
+
+    chunking: how a gathered step too big for sc_target is cut into chunks.  "reference" cuts exactly like the reference
+    (contraction.py:288-297): chunks of floor(rows / n_chunks) rows, and ONE more chunk when that leaves a remainder --
+    which holds every row only when the remainder is no longer than a chunk, i.e. roughly when rows >= n_chunks^2.  Below
+    that the chunk lists leave rows out (all of them when rows < n_chunks: chunks of 0 rows), the step's result is
+    shorter than its next_shape, and the reference's executor dies on the next row index or returns too few amplitudes;
+    tensor_contraction_sparse refuses such a scheme by name.  "cover" keeps the reference's chunk length (at least one
+    row) and emits as many chunks as it takes to hold every row: the same lists wherever the reference's hold every row."""
+    if chunking not in ("reference", "cover"):
+        raise RuntimeError(f"chunking must be 'reference' or 'cover', got {chunking!r}")
     order = ctree.tree_order_dfs()
     tensor_bonds = ctree.tn.tensor_bonds
     final_qubits = ctree.tn.final_qubits
@@ -2342,7 +2368,10 @@ def contraction_scheme_sparse(ctree, bitstrings=None, sc_target=31, labels="eins
                 n_chunks = 2 ** ceil(max(0, np.log2(len(rows)) + max(len(bond_i), len(bond_j)) - (sc_target - 2)))
                 if n_chunks > 1:
                     length = int(len(rows) / n_chunks)
-                    if len(rows) % n_chunks > 0:
+                    if chunking == "cover":
+                        length = max(1, length)
+                        n_chunks = -(-len(rows) // length)
+                    elif len(rows) % n_chunks > 0:
                         n_chunks += 1
                     batch_seq = [
                         [batch_seq[0][0][c * length:(c + 1) * length] for c in range(n_chunks)],

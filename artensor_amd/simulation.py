@@ -982,7 +982,11 @@ class TensorNetworkSimulation:
         return self
 
     def update_scheme(self, sc_target=30, bitstrings=[]):
-        """Reference simulation.py:79-88, with this package's compilers."""
+        """Reference simulation.py:79-88, with this package's compilers.  The sparse compiler's `chunking` keyword does not
+        go through here, nor through tensor_network_contraction / quantum_circuit_simulation (their parameters are the
+        reference's): chunked steps are cut like the reference's, and a scheme whose chunks leave rows out is refused by
+        tensor_contraction_sparse.  For such a plan, set `self.scheme` from contraction_scheme_sparse(...,
+        chunking="cover"), which leaves output_bonds and bitstrings_sorted as they are."""
         from copy import deepcopy
         from .contraction import contraction_scheme, contraction_scheme_sparse
         if self.pattern == "normal":

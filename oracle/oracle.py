@@ -20,6 +20,8 @@ random-network cases, including the reference's own known-answer table
 (/root/reference/tests/test_circuits.py:25-31) and Google's n30 amplitudes
 (/root/reference/examples/amplitudes_n30_m14_s0_e0_pEFGH_10000.txt).
 """
+from collections import Counter
+
 import numpy as np
 
 
@@ -70,7 +72,8 @@ def einsum_pair(eq, a, b):
     c2 = np.matmul(a2, b2)
     cur = batch + free_a + free_b
     c = c2.reshape([dim[x] for x in cur])
-    assert sorted(cur) == sorted(lo), (eq, cur, lo)
+    # (label tuples mix bond names with the batch labels -1, -2, -3: hashable, not mutually sortable)
+    assert Counter(cur) == Counter(lo), (eq, cur, lo)
     return c.transpose([cur.index(x) for x in lo]).copy(order="C")
 
 

@@ -435,3 +435,137 @@ def emulate_xgemm(eq, a, b, n_cu=None, rows16=False):
     assert rc == 0, rc
     names = ("amode", "bmode", "trans", "swapped", "nb", "flush_chunks", "kc", "rowmode", "tail_nb")
     return out, {name: getattr(info, name) for name, _ in N.ArtnStepInfo._fields_}, dict(zip(names, modes))
+
+
+# ---- test double of the reference ContractionTree, rebuilt from a tests/golden/trees.json record ----------------------
+class Vertex:
+    def __init__(self, rec, verts):
+        self.contain_tensors = frozenset(rec["contain_tensors"])
+        self.contain_bonds = list(rec["contain_bonds"])  # iteration order the reference saw
+        self.sc = rec["sc"]
+        self.left = Vertex(verts[rec["left"]], verts) if rec["left"] else None
+        self.right = Vertex(verts[rec["right"]], verts) if rec["right"] else None
+        self.rep_tensor = -1
+
+    def is_leaf(self):
+        return not (self.left and self.right)
+
+
+class TN:
+    def __init__(self, rec):
+        self.tensor_bonds = {int(k): list(v) for k, v in rec["tensor_bonds"].items()}
+        self.final_qubits = list(rec["final_qubits"])
+
+
+class Tree:
+    """Test double of the reference ContractionTree: the attributes and the two traversal
+    helpers the scheme compilers call."""
+
+    def __init__(self, rec):
+        self.tn = TN(rec)
+        root = Vertex(rec["vertices"][rec["root"]], rec["vertices"])
+        self.all_tensors = root.contain_tensors
+        self.tree = {self.all_tensors: root}
+
+    def _post_order(self):
+        out, stack = [], [self.tree[self.all_tensors]]
+        while stack:
+            v = stack.pop()
+            out.append(v)
+            if not v.is_leaf():
+                stack += [v.left, v.right]
+        return reversed(out)
+
+    def mark_rep_tensor(self):  # contraction_tree.py:305-314
+        for v in self._post_order():
+            if v.is_leaf():
+                v.rep_tensor = min(v.contain_tensors)
+            else:
+                v.rep_tensor = v.left.rep_tensor if v.left.sc > v.right.sc else v.right.rep_tensor
+
+    def tree_order_dfs(self):  # contraction_tree.py:334-357
+        self.mark_rep_tensor()
+        order, stack = [], [self.tree[self.all_tensors]]
+        while stack:
+            v = stack.pop()
+            if v.is_leaf():
+                continue
+            if v.rep_tensor == v.left.rep_tensor:
+                order.append((v.left.rep_tensor, v.right.rep_tensor))
+            else:
+                order.append((v.right.rep_tensor, v.left.rep_tensor))
+            stack += [v.left, v.right] if v.left.sc > v.right.sc else [v.right, v.left]
+        order.reverse()
+        return order
+
+
+# ---- the n12 sparse-state pattern on arbitrary bitstring sets (test_sparse_property_cpu / _gpu) -----------------------
+SC_UNCHUNKED = (31, 30, 12)     # every step with rows on both sides is an outer product, optionally row-selected
+SC_CHUNKED = (10, 8, 6, 5)      # the last steps gather matching row pairs, in chunks
+SC_TARGETS = SC_UNCHUNKED + SC_CHUNKED
+AMP_RMS = 2.0 ** -6             # rms amplitude of a 12-qubit state: the floor of amp_rel's denominator
+_n12 = None
+
+
+def n12_sparse_pattern():
+    """(tree record, leaves as a Case, the reference's state vector) of the n12 sparse-state pattern.  The leaves do not
+    depend on the bitstring set, so for any set S: compile for S, execute, and the result is state_vec[sorted(set(S))]."""
+    global _n12
+    if _n12 is None:
+        import json
+        from artensor_amd.fixtures import load_case
+        with open(os.path.join(GOLDEN, "trees.json")) as f:
+            rec = json.load(f)["n12_sparse"]
+        state = load_case(os.path.join(GOLDEN, "n12_dense.npz")).arrays["state_vec"].reshape(-1)
+        _n12 = (rec, load_case(os.path.join(GOLDEN, "n12_sparse5.npz")), state)
+    return _n12
+
+
+def bitstring_sets():
+    """name -> list of 12-bit strings, unsorted, from fixed seeds.  Which branch a step of the sparse executor takes
+    depends on the set: how many strings share a prefix, whether a row list is 0..n-1 or has one entry."""
+    width = 12
+    bits = lambda v: format(int(v), "0%db" % width)
+    sets = {}
+    for k, n in enumerate((1, 2, 3, 5, 7, 37, 200, 1000, 4095, 4096)):
+        sets["rand%d" % n] = [bits(v) for v in np.random.default_rng(100 + k).choice(2 ** width, n, replace=False)]
+    few = [bits(v) for v in np.random.default_rng(120).choice(2 ** width, 9, replace=False)]
+    sets["duplicates"] = few + few[2:6] + few[:1]
+    sets["zeros_and_ones"] = ["0" * width, "1" * width]
+    sets["msb6_shared"] = [bits((0b101100 << 6) | v) for v in np.random.default_rng(121).permutation(64)]
+    sets["lsb6_shared"] = [bits((int(v) << 6) | 0b010011) for v in np.random.default_rng(122).permutation(64)]
+    sets["middle_qubit_pair"] = [bits(0b110100101101), bits(0b110100101101 ^ (1 << 6))]
+    sets["fixture40"] = list(n12_sparse_pattern()[0]["bitstrings"])
+    return sets
+
+
+def other_set_of_the_same_size(name, seed=7):
+    """A different bitstring set with as many distinct strings as bitstring_sets()[name] has."""
+    n = len(set(bitstring_sets()[name]))
+    return [format(int(v), "012b") for v in np.random.default_rng(1000 + seed + n).choice(4096, n, replace=False)]
+
+
+def compile_n12_sparse(bitstrings, sc_target, labels="einsum", chunking="reference"):
+    import artensor_amd as A
+    return A.contraction_scheme_sparse(Tree(n12_sparse_pattern()[0]["tree"]), bitstrings, sc_target=sc_target,
+                                       labels=labels, chunking=chunking)
+
+
+def rows_left_out(scheme):
+    """REFERENCE_CHUNKS_LEAVE_ROWS_OUT: the (step, chunks, rows held, rows of the result) of every chunked step whose
+    chunk lists hold fewer rows than its result has -- what the reference's chunk split (contraction.py:288-297: chunks of
+    floor(rows / n) rows, plus one when there is a remainder) emits when a step has fewer rows than about n^2.  The
+    reference's own executor cannot run such a scheme: it dies at the next row index past the short result, or returns
+    fewer amplitudes than bitstrings."""
+    return [(n, len(s[2][0]), sum(len(x) for x in s[2][0]), s[4][0]) for n, s in enumerate(scheme)
+            if len(s) > 4 and len(s[2][0]) > 1 and sum(len(x) for x in s[2][0]) != s[4][0]]
+
+
+def oracle_sparse(scheme, dtype=np.complex64, scientific_notation=False):
+    """The oracle on the n12 leaves: (amplitudes, factor) -- factor None without scientific_notation."""
+    from oracle import oracle
+    leaves = {i: t.numpy().astype(dtype) for i, t in n12_sparse_pattern()[1].tensors.items()}
+    got = oracle.tensor_contraction_sparse(leaves, scheme, scientific_notation=scientific_notation)
+    if scientific_notation:
+        return np.asarray(got[1]).reshape(-1), float(np.real(got[0]))
+    return np.asarray(got).reshape(-1), None

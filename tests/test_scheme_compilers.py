@@ -1,8 +1,8 @@
 """Scheme compilers (artensor_amd.contraction_scheme / contraction_scheme_sparse) against the
 schemes the reference compiled from the same trees (tests/golden/trees.json, produced by
 tests/golden/make_golden.py::case_trees).  The planner is not part of this package, so the
-tree is rebuilt here as a plain test double exposing exactly what the compilers consume
-(reference contraction_tree.py:10-50, :305-314, :334-357)."""
+tree is rebuilt as a plain test double exposing exactly what the compilers consume
+(helpers.Tree; reference contraction_tree.py:10-50, :305-314, :334-357)."""
 import json
 import os
 
@@ -10,69 +10,9 @@ import numpy as np
 import pytest
 
 import artensor_amd as A
+from helpers import Tree
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-class Vertex:
-    def __init__(self, rec, verts):
-        self.contain_tensors = frozenset(rec["contain_tensors"])
-        self.contain_bonds = list(rec["contain_bonds"])  # iteration order the reference saw
-        self.sc = rec["sc"]
-        self.left = Vertex(verts[rec["left"]], verts) if rec["left"] else None
-        self.right = Vertex(verts[rec["right"]], verts) if rec["right"] else None
-        self.rep_tensor = -1
-
-    def is_leaf(self):
-        return not (self.left and self.right)
-
-
-class TN:
-    def __init__(self, rec):
-        self.tensor_bonds = {int(k): list(v) for k, v in rec["tensor_bonds"].items()}
-        self.final_qubits = list(rec["final_qubits"])
-
-
-class Tree:
-    """Test double of the reference ContractionTree: the attributes and the two traversal
-    helpers the scheme compilers call."""
-
-    def __init__(self, rec):
-        self.tn = TN(rec)
-        root = Vertex(rec["vertices"][rec["root"]], rec["vertices"])
-        self.all_tensors = root.contain_tensors
-        self.tree = {self.all_tensors: root}
-
-    def _post_order(self):
-        out, stack = [], [self.tree[self.all_tensors]]
-        while stack:
-            v = stack.pop()
-            out.append(v)
-            if not v.is_leaf():
-                stack += [v.left, v.right]
-        return reversed(out)
-
-    def mark_rep_tensor(self):  # contraction_tree.py:305-314
-        for v in self._post_order():
-            if v.is_leaf():
-                v.rep_tensor = min(v.contain_tensors)
-            else:
-                v.rep_tensor = v.left.rep_tensor if v.left.sc > v.right.sc else v.right.rep_tensor
-
-    def tree_order_dfs(self):  # contraction_tree.py:334-357
-        self.mark_rep_tensor()
-        order, stack = [], [self.tree[self.all_tensors]]
-        while stack:
-            v = stack.pop()
-            if v.is_leaf():
-                continue
-            if v.rep_tensor == v.left.rep_tensor:
-                order.append((v.left.rep_tensor, v.right.rep_tensor))
-            else:
-                order.append((v.right.rep_tensor, v.left.rep_tensor))
-            stack += [v.left, v.right] if v.left.sc > v.right.sc else [v.right, v.left]
-        order.reverse()
-        return order
 
 
 def canon(eq):
