@@ -59,6 +59,13 @@ from .rdm import (  # noqa: F401
     reduced_density_matrix,
     renyi_entropy,
 )
+from . import pauli  # noqa: F401
+from .pauli import (  # noqa: F401
+    pauli_expectation,
+    pauli_info,
+    pauli_ops,
+    pauli_sum_expectation,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

@@ -107,6 +107,17 @@ class ArtnRdmInfo(ctypes.Structure):
     ]
 
 
+class ArtnPauliInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_groups", ctypes.c_int32),
+        ("n_launches", ctypes.c_int32),
+        ("terms_per_launch", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("workspace_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -165,6 +176,12 @@ _EXPORTS = {
     "artn_rdm_row_offsets": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p]),
     "artn_rdm": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 (a library built before them lacks both: has("artn_pauli_expect"))
+    "artn_pauli_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.POINTER(ArtnPauliInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p]),
+    "artn_pauli_expect": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

@@ -17,6 +17,9 @@
 // K consecutive entries sequentially (local[]), one thread scans the per-thread totals sequentially (base[]), then
 // P[i] = fl(base[k] + local[i]).  Because total[k] IS local[last of k], P is non-decreasing across thread boundaries too, and
 // P[i] > P[i-1] only where entry i is non-zero: a bisection for "smallest i with P[i] > r" always lands on a non-zero entry.
+//
+// (artn_pauli_kernel.h includes this header for born_wg_tree and the term helpers: the kernels that are no templates are `static`,
+// so that a second translation unit neither emits nor redefines them.)
 #ifndef ARTN_BORN_KERNEL_H
 #define ARTN_BORN_KERNEL_H
 
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_overlap(const T
 }
 
 // out4 = {Re, Im, |a|^2, |b|^2}; nv = 1: the partials hold |a|^2 alone and out4 = {|a|^2, 0, |a|^2, |a|^2}
-__global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_finish(const double *__restrict__ partial, int n_partial, int nv,
+static __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_finish(const double *__restrict__ partial, int n_partial, int nv,
                                                                         double *__restrict__ out4) {
   __shared__ double red[ARTN_BORN_THREADS][4];
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -211,7 +214,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_block_sums(cons
   if (threadIdx.x == 0) block_sum[blockIdx.x] = pseg[BORN_PIDX((1 << (bbits - 2)) - 1)];
 }
 
-__global__ __launch_bounds__(ARTN_BORN_PREFIX_THREADS) void artn_k_born_prefix(const double *__restrict__ block_sum,
+static __global__ __launch_bounds__(ARTN_BORN_PREFIX_THREADS) void artn_k_born_prefix(const double *__restrict__ block_sum,
                                                                                double *__restrict__ prefix, long nb) {
   __shared__ double tot[ARTN_BORN_PREFIX_THREADS];
   const int tid = threadIdx.x;
@@ -380,7 +383,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_marginal_stream(cons
   }
 }
 
-__global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_marginal_finish(const double *__restrict__ ws, ArtnMargStream p,
+static __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_marginal_finish(const double *__restrict__ ws, ArtnMargStream p,
                                                                             double *__restrict__ out) {
   const long o = (long)blockIdx.x * ARTN_BORN_THREADS + threadIdx.x;
   if (o >= ((long)1 << p.kept_bits)) return;

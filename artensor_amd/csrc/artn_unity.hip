@@ -20,3 +20,4 @@
 #endif
 #include "artn_born.hip"
 #include "artn_rdm.hip"
+#include "artn_pauli.hip"

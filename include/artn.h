@@ -344,6 +344,37 @@ int artn_rdm_query(const ArtnMarginalDesc *d, ArtnRdmInfo *info);
 int artn_rdm_row_offsets(const ArtnMarginalDesc *d, int64_t *offset);
 int artn_rdm(const ArtnMarginalDesc *d, const void *a, double *out /* [D][D][2] */, void *ws, int64_t ws_bytes, void *stream);
 
+/*
+ * Expectation values of Pauli strings (additive to ABI 9: look the symbols up before calling).  For a DENSE tensor of
+ * power-of-two extents (descriptor and density checks of artn_marginal; dimensions in the caller's order, keep[] ignored), a
+ * string gives every dimension one of I, X, Y, Z: `ops` is uint8 [n_terms][n_dims], 0..3 = I, X, Y, Z; X, Y and Z only on
+ * dimensions of extent 2.  A dimension of extent 2 and stride 2^b is bit b of the flat memory index; with xmask the bits under
+ * X or Y, zmask those under Z or Y and n_y the number of Y,
+ *     <psi|P|psi> = sum_i conj(a[i ^ xmask]) * i^n_y * (-1)^popcount(i & zmask) * a[i]        (real)
+ * one streaming pass over the amplitudes for up to terms_per_launch strings of equal xmask (a GROUP; groups are numbered in the
+ * order they first appear).  A call takes sum over groups of ceil(count / terms_per_launch) launches, each reading every
+ * amplitude once.  Terms are formed in float64 (complex64 values are converted first), sums are float64 in an order that depends
+ * on the element count and the masks alone, without floating-point atomics: bit-identical from run to run.
+ * ARTN_E_INVALID: a layout that is not dense, an operator code above 3, X/Y/Z on an extent other than 2, n_terms < 1, a workspace
+ * that is too small.  ARTN_E_UNSUPPORTED: an extent that is no power of two, more than 96 dimensions, more than 2^40 elements.
+ */
+typedef struct ArtnPauliInfo {
+  int32_t n_groups;         /* distinct xmasks                                        */
+  int32_t n_launches;       /* passes over the amplitudes                             */
+  int32_t terms_per_launch; /* strings one pass serves                                */
+  int32_t reserved;
+  int64_t workspace_bytes;
+  int64_t bytes_read;       /* n_launches * bytes of the state                        */
+} ArtnPauliInfo;
+/* Host-only: validates, translates every term to memory-bit masks, groups by xmask, sizes the workspace.
+ * xmask, zmask, n_y, group: n_terms entries each, any of them may be NULL. */
+int artn_pauli_query(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_terms, ArtnPauliInfo *info, uint64_t *xmask,
+                     uint64_t *zmask, int32_t *n_y, int32_t *group);
+/* out (device, float64 [n_terms + 1]): the raw sums in the caller's term order, out[n_terms] = sum |a|^2 (from the first pass).
+ * `a` must be 16-byte aligned.  No allocation, copy or synchronisation: the launches are enqueued on `stream`. */
+int artn_pauli_expect(const ArtnMarginalDesc *d, const void *a, const uint8_t *ops, int64_t n_terms, double *out, void *ws,
+                      int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
