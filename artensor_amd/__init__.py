@@ -61,10 +61,16 @@ from .rdm import (  # noqa: F401
 )
 from . import pauli  # noqa: F401
 from .pauli import (  # noqa: F401
+    PauliSumOperator,
+    pauli_apply,
+    pauli_apply_info,
     pauli_expectation,
     pauli_info,
     pauli_ops,
+    pauli_rotate,
+    pauli_sum_apply,
     pauli_sum_expectation,
+    pauli_sum_variance,
 )
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401

@@ -118,6 +118,18 @@ class ArtnPauliInfo(ctypes.Structure):
     ]
 
 
+class ArtnPauliApplyInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_groups", ctypes.c_int32),
+        ("n_xmask_hi", ctypes.c_int32),
+        ("n_launches", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("table_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -182,6 +194,14 @@ _EXPORTS = {
                                         ctypes.c_void_p]),
     "artn_pauli_expect": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: y = H a (has("artn_pauli_apply"))
+    "artn_pauli_apply_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.POINTER(ArtnPauliApplyInfo), ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_pauli_apply_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_int64]),
+    "artn_pauli_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

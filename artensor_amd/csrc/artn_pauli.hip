@@ -1,4 +1,5 @@
-// artn_pauli.hip -- host half of the Pauli-string entry points of include/artn.h (kernels: artn_pauli_kernel.h).
+// artn_pauli.hip -- host half of the Pauli-string entry points of include/artn.h (kernels: artn_pauli_kernel.h for the
+// expectation values, artn_pauli_apply_kernel.h for y = H a).
 //
 // A translation unit of its own (build/obj/pauli.o).
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 
 #include "artn_host.h"
 #include "artn_pauli_kernel.h"
+#include "artn_pauli_apply_kernel.h"
 
 struct PauliPlan {
   int64_t n = 1;
@@ -119,7 +121,122 @@ static void pauli_launch(const PauliPlan &pl, const T *a, ArtnPauliArgs &p, cons
   hipLaunchKernelGGL(artn_k_pauli_finish, dim3(1), dim3(64), 0, st, (const double *)part, n_partial, nv, f, out);
 }
 
+// y = H a: the groups of a plan in summation order (stable by xm_hi), the folded coefficients, the table.
+struct PauliApplyPlan {
+  PauliPlan pl;
+  std::vector<int32_t> order, pos; // order[p] = the group at position p; pos[g] = the position of group g
+  std::vector<double> folded;      // [n_terms][2]: c_k (-i)^ny_k
+  ArtnPauliApplyInfo info = {};
+};
+
+static int pauli_apply_plan(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_terms, PauliApplyPlan &ap) {
+  if (int rc = pauli_plan(d, ops, n_terms, ap.pl)) return rc;
+  const PauliPlan &pl = ap.pl;
+  const int32_t ng = (int32_t)pl.members.size();
+  auto hi = [&](int32_t g) { return pl.xm[pl.members[g][0]] >> ARTN_PAULI_TILE_BITS; };
+  ap.order.resize(ng), ap.pos.resize(ng);
+  for (int32_t g = 0; g < ng; ++g) ap.order[g] = g;
+  std::stable_sort(ap.order.begin(), ap.order.end(), [&](int32_t x, int32_t y) { return hi(x) < hi(y); });
+  int32_t n_hi = 0;
+  for (int32_t p = 0; p < ng; ++p) {
+    ap.pos[ap.order[p]] = p;
+    if (p == 0 || hi(ap.order[p]) != hi(ap.order[p - 1])) ++n_hi;
+  }
+  ap.folded.resize(2 * n_terms);
+  for (int64_t t = 0; t < n_terms; ++t) {
+    const double re = coeff ? coeff[2 * t] : 1.0, im = coeff ? coeff[2 * t + 1] : 0.0;
+    double *f = &ap.folded[2 * t];
+    switch (pl.ny[t] & 3) { // c (-i)^ny
+    case 0: f[0] = re, f[1] = im; break;
+    case 1: f[0] = im, f[1] = -re; break;
+    case 2: f[0] = -re, f[1] = -im; break;
+    default: f[0] = -im, f[1] = re; break;
+    }
+  }
+  const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16;
+  ap.info.n_groups = ng;
+  ap.info.n_xmask_hi = n_hi;
+  ap.info.n_launches = 1;
+  ap.info.table_bytes = (int64_t)sizeof(ArtnPauliApplyHeader) * (1 + (int64_t)ng + n_terms);
+  ap.info.bytes_read = ap.info.bytes_written = pl.n * elem;
+  return ARTN_OK;
+}
+
+template <typename T>
+static void pauli_apply_launch(const PauliPlan &pl, const T *a, T *y, const ArtnPauliApplyGroup *grp, const ArtnPauliApplyTerm *trm,
+                               int n_groups, hipStream_t st) {
+  const dim3 block(ARTN_BORN_THREADS);
+  if (pl.n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
+    hipLaunchKernelGGL(artn_k_pauli_apply_small<T>, dim3(1), block, 0, st, a, y, (long)pl.n, grp, trm, n_groups);
+  } else {
+    const long tiles = (long)(pl.n >> ARTN_PAULI_TILE_BITS);
+    const dim3 grid((unsigned)std::min<long>(tiles, ARTN_PAULI_APPLY_MAX_GRID));
+    hipLaunchKernelGGL(artn_k_pauli_apply<T>, grid, block, 0, st, a, y, tiles, grp, trm, n_groups);
+  }
+}
+
 extern "C" {
+
+int artn_pauli_apply_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_terms,
+                           ArtnPauliApplyInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *group, double *folded,
+                           uint64_t *group_xmask, int32_t *group_pos) {
+  if (!info) return fail(ARTN_E_INVALID, "null info");
+  PauliApplyPlan ap;
+  if (int rc = pauli_apply_plan(d, ops, coeff, n_terms, ap)) return rc;
+  const PauliPlan &pl = ap.pl;
+  *info = ap.info;
+  if (xmask) std::copy(pl.xm.begin(), pl.xm.end(), xmask);
+  if (zmask) std::copy(pl.zm.begin(), pl.zm.end(), zmask);
+  if (n_y) std::copy(pl.ny.begin(), pl.ny.end(), n_y);
+  if (group) std::copy(pl.group.begin(), pl.group.end(), group);
+  if (folded) std::copy(ap.folded.begin(), ap.folded.end(), folded);
+  if (group_xmask)
+    for (size_t g = 0; g < pl.members.size(); ++g) group_xmask[g] = pl.xm[pl.members[g][0]];
+  if (group_pos) std::copy(ap.pos.begin(), ap.pos.end(), group_pos);
+  return ARTN_OK;
+}
+
+int artn_pauli_apply_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_terms, void *table,
+                          int64_t table_bytes) {
+  PauliApplyPlan ap;
+  if (int rc = pauli_apply_plan(d, ops, coeff, n_terms, ap)) return rc;
+  if (!table) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_apply_query reports");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_apply_pack needs an 8-byte aligned table");
+  const PauliPlan &pl = ap.pl;
+  ArtnPauliApplyHeader *h = (ArtnPauliApplyHeader *)table;
+  ArtnPauliApplyGroup *grp = (ArtnPauliApplyGroup *)(h + 1);
+  ArtnPauliApplyTerm *trm = (ArtnPauliApplyTerm *)(grp + pl.members.size());
+  *h = ArtnPauliApplyHeader{(uint64_t)pl.members.size(), (uint64_t)n_terms, (uint64_t)ap.info.n_xmask_hi, 0};
+  uint64_t at = 0;
+  for (size_t p = 0; p < ap.order.size(); ++p) {
+    const auto &m = pl.members[ap.order[p]];
+    grp[p] = ArtnPauliApplyGroup{pl.xm[m[0]], at, (uint64_t)m.size(), 0};
+    for (int64_t t : m) trm[at++] = ArtnPauliApplyTerm{pl.zm[t], pl.zm[t] & 3, ap.folded[2 * t], ap.folded[2 * t + 1]};
+  }
+  return ARTN_OK;
+}
+
+int artn_pauli_apply(const ArtnMarginalDesc *d, const void *a, void *y, const uint8_t *ops, int64_t n_terms, const void *table,
+                     int64_t table_bytes, void *stream) {
+  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
+  PauliApplyPlan ap;
+  if (int rc = pauli_apply_plan(d, ops, nullptr, n_terms, ap)) return rc; // (the coefficients are in the table)
+  if (!a || !y || !table) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_apply_query reports");
+  if ((((uintptr_t)a | (uintptr_t)y) & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_apply needs 16-byte aligned arrays");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_apply needs an 8-byte aligned table");
+  const uintptr_t bytes = (uintptr_t)ap.info.bytes_read, pa = (uintptr_t)a, py = (uintptr_t)y;
+  if (pa < py + bytes && py < pa + bytes) return fail(ARTN_E_INVALID, "artn_pauli_apply: y overlaps a (there is no in-place form)");
+  const int ng = ap.info.n_groups;
+  const ArtnPauliApplyGroup *grp = (const ArtnPauliApplyGroup *)((const ArtnPauliApplyHeader *)table + 1);
+  const ArtnPauliApplyTerm *trm = (const ArtnPauliApplyTerm *)(grp + ng);
+  hipStream_t st = (hipStream_t)stream;
+  if (d->dtype == ARTN_C64) pauli_apply_launch(ap.pl, (const float2 *)a, (float2 *)y, grp, trm, ng, st);
+  else pauli_apply_launch(ap.pl, (const double2 *)a, (double2 *)y, grp, trm, ng, st);
+  HIP_TRY(hipGetLastError());
+  return ARTN_OK;
+}
 
 int artn_pauli_query(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_terms, ArtnPauliInfo *info, uint64_t *xmask,
                      uint64_t *zmask, int32_t *n_y, int32_t *group) {

@@ -1,5 +1,6 @@
 """Expectation values of Pauli strings and of sums of them (Hamiltonians) on an amplitude tensor on the device (C ABI:
-artn_pauli_query, artn_pauli_expect).
+artn_pauli_query, artn_pauli_expect), and the same operators APPLIED to the tensor: y = H a in one launch (artn_pauli_apply_query,
+artn_pauli_apply_pack, artn_pauli_apply).
 
 A Pauli string gives every dim of `amps` one of I, X, Y, Z -- X, Y and Z only on dims of extent 2, every other dim (a row
 dimension, an extent-1 dim) carries I.  It is written either as a `str` of length amps.dim() over "IXYZ" (any case; character d
@@ -17,9 +18,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked
+from .born import _DTYPES, _checked, norm2, overlap
 
-__all__ = ["pauli_ops", "pauli_info", "pauli_expectation", "pauli_sum_expectation"]
+__all__ = ["pauli_ops", "pauli_info", "pauli_expectation", "pauli_sum_expectation", "pauli_apply_info", "PauliSumOperator",
+           "pauli_sum_apply", "pauli_apply", "pauli_rotate", "pauli_sum_variance"]
 
 _CODES = {"I": 0, "X": 1, "Y": 2, "Z": 3}
 
@@ -138,3 +140,137 @@ def pauli_sum_expectation(amps, terms, normalize=True):
     if all(c.imag == 0.0 for c in coeffs):
         return float(np.dot(np.array([c.real for c in coeffs]), vals))
     return complex(np.dot(np.array(coeffs), vals))
+
+
+# ---- y = H a ----------------------------------------------------------------------------------------------------------------
+def _split_terms(terms, n_dims):
+    """([n_terms, 2] float64 coefficients, uint8 ops) of terms = [(c_k, string_k), ...]."""
+    terms = list(terms)
+    if not terms:
+        raise ValueError("at least one term is needed")
+    coeff = np.array([[complex(c).real, complex(c).imag] for c, _ in terms], dtype=np.float64)
+    ops, _ = pauli_ops([p for _, p in terms], n_dims)
+    return np.ascontiguousarray(coeff), ops
+
+
+def _ptr(x):
+    return x.ctypes.data_as(ctypes.c_void_p)
+
+
+def _apply_query(d, ops, coeff, arrays=False):
+    n_terms = ops.shape[0]
+    info = _native.ArtnPauliApplyInfo()
+    if arrays:
+        xm, zm, gx = (np.zeros(n_terms, dtype=np.uint64) for _ in range(3))
+        ny, group, pos = (np.zeros(n_terms, dtype=np.int32) for _ in range(3))
+        folded = np.zeros((n_terms, 2), dtype=np.float64)
+        out = (xm, zm, ny, group, folded, gx, pos)
+        ptrs = [_ptr(x) for x in out]
+    else:
+        out, ptrs = (), [None] * 7
+    _native.check(_native.lib().artn_pauli_apply_query(ctypes.byref(d), _ptr(ops), _ptr(coeff), n_terms, ctypes.byref(info), *ptrs))
+    return (info,) + out
+
+
+def pauli_apply_info(shape, strides, terms, dtype=torch.complex64):
+    """Host-only: what one call of y = H a does for terms = [(c_k, string_k), ...].  Per term: xmask, zmask, n_y, group and the
+    folded coefficient c_k (-i)^n_y (complex).  Per group (numbered as they first appear): group_xmask and group_pos, its position
+    in the summation order of every output element; group_order lists the groups in that order.  n_xmask_hi: the partner tiles
+    fetched per output tile; table_bytes; the nominal bytes_read and bytes_written; n_launches (1)."""
+    if dtype not in _DTYPES:
+        raise TypeError(f"pauli_apply_info: complex64 or complex128 expected, got {dtype}")
+    coeff, ops = _split_terms(terms, len(shape))
+    info, xm, zm, ny, group, folded, gx, pos = _apply_query(_desc(shape, strides, dtype), ops, coeff, arrays=True)
+    ng = info.n_groups
+    pos = [int(v) for v in pos[:ng]]
+    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny], "group": [int(v) for v in group],
+            "folded": [complex(r, i) for r, i in folded], "n_groups": ng, "group_xmask": [int(v) for v in gx[:ng]], "group_pos": pos,
+            "group_order": [int(g) for g in np.argsort(pos)], "n_xmask_hi": info.n_xmask_hi, "table_bytes": info.table_bytes,
+            "bytes_read": info.bytes_read, "bytes_written": info.bytes_written, "n_launches": info.n_launches}
+
+
+def _pack(d, ops, coeff):
+    """The term table (include/artn.h) as a uint8 numpy array."""
+    info = _apply_query(d, ops, coeff)[0]
+    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
+    _native.check(_native.lib().artn_pauli_apply_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], _ptr(table), info.table_bytes))
+    return table.view(np.uint8), info
+
+
+class PauliSumOperator:
+    """H = sum_k c_k P_k (terms = [(c_k, string_k), ...], complex coefficients allowed) for tensors of one layout: validates,
+    packs the term table and copies it to `device` once; op(amps, out=None) is then one launch that writes H|amps> in the layout of
+    amps.  `amps` is read in place and never written."""
+
+    def __init__(self, shape, strides, dtype, terms, device):
+        if dtype not in _DTYPES:
+            raise TypeError(f"PauliSumOperator: complex64 or complex128 expected, got {dtype}")
+        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"PauliSumOperator: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU "
+                               "fallback")
+        coeff, self._ops = _split_terms(terms, len(self.shape))
+        self._d = _desc(self.shape, self.strides, dtype)
+        table, info = _pack(self._d, self._ops, coeff)
+        self.n_terms, self.n_groups, self.table_bytes = self._ops.shape[0], info.n_groups, info.table_bytes
+        self._table = torch.from_numpy(table).to(self.device)
+
+    def __call__(self, amps, out=None):
+        what = "pauli.PauliSumOperator"
+        n = _checked(amps, what)
+        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
+            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
+                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
+        if amps.device != self._table.device:
+            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        if out is None:
+            out = torch.empty_strided(self.shape, self.strides, dtype=self.dtype, device=amps.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != amps.dtype or out.device != amps.device \
+                    or tuple(out.shape) != self.shape or tuple(out.stride()) != self.strides:
+                raise ValueError(f"{what}: out must have the shape, strides, dtype and device of amps")
+            nbytes = n * amps.element_size()
+            if out.data_ptr() < amps.data_ptr() + nbytes and amps.data_ptr() < out.data_ptr() + nbytes:
+                raise ValueError(f"{what}: out overlaps amps (there is no in-place form)")
+            if out.data_ptr() % 16:
+                raise ValueError(f"{what}: out must start on a 16-byte boundary")
+        with torch.cuda.device(amps.device):
+            _native.check(_native.lib().artn_pauli_apply(ctypes.byref(self._d), amps.data_ptr(), out.data_ptr(), _ptr(self._ops),
+                                                         self.n_terms, self._table.data_ptr(), self.table_bytes,
+                                                         _native.current_stream_ptr(amps.device)))
+        return out
+
+
+def pauli_sum_apply(amps, terms, out=None):
+    """H|amps> for H = sum_k c_k P_k, terms = [(c_k, string_k), ...]: one launch; the result has the shape, strides and dtype of
+    amps (out=None allocates it)."""
+    _checked(amps, "pauli.pauli_sum_apply")
+    return PauliSumOperator(amps.shape, amps.stride(), amps.dtype, terms, amps.device)(amps, out)
+
+
+def pauli_apply(amps, string, out=None):
+    """P|amps> for one Pauli string."""
+    _checked(amps, "pauli.pauli_apply")
+    return PauliSumOperator(amps.shape, amps.stride(), amps.dtype, [(1.0, string)], amps.device)(amps, out)
+
+
+def pauli_rotate(amps, string, theta, out=None):
+    """exp(-i theta P)|amps> = cos(theta) amps - i sin(theta) P amps: a two-term sum (I, P), one launch, out of place."""
+    _checked(amps, "pauli.pauli_rotate")
+    theta = float(theta)
+    terms = [(np.cos(theta), {}), (-1j * np.sin(theta), string)]
+    return PauliSumOperator(amps.shape, amps.stride(), amps.dtype, terms, amps.device)(amps, out)
+
+
+def pauli_sum_variance(amps, terms):
+    """(E, var) of H = sum_k c_k P_k with REAL coefficients: E = Re<a|Ha> / |a|^2 and var = |Ha|^2 / |a|^2 - E^2, from one apply,
+    one overlap and one norm."""
+    _native.require_gpu(amps, "pauli.pauli_sum_variance")
+    terms = list(terms)
+    if any(complex(c).imag != 0.0 for c, _ in terms):
+        raise ValueError("pauli_sum_variance takes real coefficients (a Hermitian sum)")
+    y = pauli_sum_apply(amps, terms)
+    aha, na, _ = overlap(amps, y)
+    e = aha.real / na
+    return e, norm2(y) / na - e * e

@@ -375,6 +375,64 @@ int artn_pauli_query(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_te
 int artn_pauli_expect(const ArtnMarginalDesc *d, const void *a, const uint8_t *ops, int64_t n_terms, double *out, void *ws,
                       int64_t ws_bytes, void *stream);
 
+/*
+ * Applying Pauli strings and sums of them to a state: y = H a, H = sum_k c_k P_k (additive to ABI 9: look the symbols up before
+ * calling).  Descriptor, `ops`, masks, checks and refusals are those of artn_pauli_query; `coeff` is float64 [n_terms][2]
+ * (Re c_k, Im c_k; NULL: every coefficient 1).  With the masks above,
+ *     (P a)[i] = (-i)^n_y * (-1)^popcount(i & zmask) * a[i ^ xmask]
+ *     y[i]     = sum over groups g of W_g(i) * a[i ^ xmask_g],   W_g(i) = sum_{k in g} f_k * (-1)^popcount(i & zmask_k)
+ * f_k = c_k (-i)^n_y the FOLDED coefficient (exact: a swap and sign changes of Re c_k, Im c_k).  `y` has the memory layout of `a`.
+ * ONE launch writes every element of y once and never reads y, whatever the number of groups and terms; `a` is only read.
+ * Products and sums are float64 for both dtypes (complex64 values are converted first), a complex64 result is rounded once.
+ * SUMMATION ORDER of every output element: the groups sorted by xmask >> 10 (the bits above a tile of 2^10 elements; one fetch of
+ * the partner tile serves all the groups that share them), ties in the order the groups first appear in the call; inside a group
+ * the terms in the caller's order (they are summed into W_g before the one multiplication by the partner).  No atomics:
+ * bit-identical from run to run.
+ *
+ * TERM TABLE (what artn_pauli_apply_pack writes and the kernel reads; 8-byte little-endian fields, 32-byte records):
+ *     record 0                      ArtnPauliApplyHeader   n_groups, n_terms, n_xmask_hi, 0
+ *     records 1 .. n_groups         ArtnPauliApplyGroup    in summation order: xmask, first, count, 0 -- the group's terms are the
+ *                                                          term records first .. first + count - 1 (numbered from 0)
+ *     then n_terms records          ArtnPauliApplyTerm     group by group in summation order, the caller's order inside a group:
+ *                                                          zmask, zmask & 3 (the sign CLASS of the four elements a thread owns),
+ *                                                          Re f_k, Im f_k as float64
+ * table_bytes = 32 * (1 + n_groups + n_terms).
+ */
+typedef struct ArtnPauliApplyHeader {
+  uint64_t n_groups, n_terms, n_xmask_hi, reserved;
+} ArtnPauliApplyHeader;
+typedef struct ArtnPauliApplyGroup {
+  uint64_t xmask, first, count, reserved;
+} ArtnPauliApplyGroup;
+typedef struct ArtnPauliApplyTerm {
+  uint64_t zmask, sign_class;
+  double re, im;
+} ArtnPauliApplyTerm;
+typedef struct ArtnPauliApplyInfo {
+  int32_t n_groups;     /* distinct xmasks                                          */
+  int32_t n_xmask_hi;   /* distinct xmask >> 10: partner tiles fetched per own tile */
+  int32_t n_launches;   /* 1                                                        */
+  int32_t reserved;
+  int64_t table_bytes;
+  int64_t bytes_read;    /* nominal: n * element size (every partner tile is a tile of `a`)  */
+  int64_t bytes_written; /* n * element size                                                  */
+} ArtnPauliApplyInfo;
+/* Host-only: validates, translates, groups and orders.  Per term (n_terms entries each, any may be NULL): xmask, zmask, n_y,
+ * group (numbered in the order the groups first appear) and folded (float64 [n_terms][2]).  Per group (n_groups <= n_terms
+ * entries each, any may be NULL; indexed by group number): group_xmask and group_pos, the group's position in summation order. */
+int artn_pauli_apply_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_terms,
+                           ArtnPauliApplyInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *group, double *folded,
+                           uint64_t *group_xmask, int32_t *group_pos);
+/* Host-only: writes the term table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_pauli_apply_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_terms, void *table,
+                          int64_t table_bytes);
+/* y = H a in one launch on `stream`.  `table` is DEVICE memory holding what artn_pauli_apply_pack wrote for the same descriptor,
+ * ops and n_terms (the caller copies it there; 8-byte aligned).  `a` and `y` are 16-byte aligned and their byte ranges do not
+ * overlap (ARTN_E_UNSUPPORTED / ARTN_E_INVALID); a table_bytes below the query's is ARTN_E_INVALID.  No allocation, copy or
+ * synchronisation.  ARTN_E_NODEVICE without a device. */
+int artn_pauli_apply(const ArtnMarginalDesc *d, const void *a, void *y, const uint8_t *ops, int64_t n_terms, const void *table,
+                     int64_t table_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
