@@ -18,7 +18,8 @@ MAIN_HDRS := $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/ar
              $(CSRC)/artn_xgemm128_kernel.h $(CSRC)/artn_xrow_kernel.h $(CSRC)/artn_xgemm_pc_kernel.h
 BORN_SRCS := $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
 RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(HOST_HDRS)
-PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pauli_apply_kernel.h $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
+PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pauli_apply_kernel.h $(CSRC)/artn_pauli_evolve_kernel.h \
+              $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
 # (the single-translation-unit builds below: artn_unity.hip includes every unit source)
 SRCS := $(CSRC)/artn_unity.hip $(CSRC)/artn_api.hip $(wildcard $(CSRC)/units/*.hip) $(HDRS) $(LAUNCH_HDRS) $(MAIN_HDRS) $(BORN_SRCS) $(RDM_SRCS) $(PAULI_SRCS)
 OBJDIR := build/obj

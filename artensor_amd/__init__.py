@@ -61,16 +61,22 @@ from .rdm import (  # noqa: F401
 )
 from . import pauli  # noqa: F401
 from .pauli import (  # noqa: F401
+    PauliCircuit,
     PauliSumOperator,
     pauli_apply,
+    pauli_apply_,
     pauli_apply_info,
+    pauli_evolve_,
+    pauli_evolve_info,
     pauli_expectation,
     pauli_info,
     pauli_ops,
     pauli_rotate,
+    pauli_rotate_,
     pauli_sum_apply,
     pauli_sum_expectation,
     pauli_sum_variance,
+    trotter_steps,
 )
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401

@@ -130,6 +130,20 @@ class ArtnPauliApplyInfo(ctypes.Structure):
     ]
 
 
+class ArtnPauliEvolveInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_runs", ctypes.c_int32),
+        ("n_launches", ctypes.c_int32),
+        ("max_rank", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("table_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
+PAULI_EVOLVE_MAX_RANK = 4
+
 _lib = None
 _lock = threading.Lock()
 
@@ -202,6 +216,15 @@ _EXPORTS = {
                                              ctypes.c_void_p, ctypes.c_int64]),
     "artn_pauli_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: in-place circuits of Pauli steps (has("artn_pauli_evolve"))
+    "artn_pauli_evolve_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_int32, ctypes.POINTER(ArtnPauliEvolveInfo), ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+    "artn_pauli_evolve_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
+    "artn_pauli_evolve": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

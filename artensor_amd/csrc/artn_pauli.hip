@@ -1,5 +1,5 @@
 // artn_pauli.hip -- host half of the Pauli-string entry points of include/artn.h (kernels: artn_pauli_kernel.h for the
-// expectation values, artn_pauli_apply_kernel.h for y = H a).
+// expectation values, artn_pauli_apply_kernel.h for y = H a, artn_pauli_evolve_kernel.h for the in-place circuits).
 //
 // A translation unit of its own (build/obj/pauli.o).
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include "artn_host.h"
 #include "artn_pauli_kernel.h"
 #include "artn_pauli_apply_kernel.h"
+#include "artn_pauli_evolve_kernel.h"
 
 struct PauliPlan {
   int64_t n = 1;
@@ -287,6 +288,194 @@ int artn_pauli_expect(const ArtnMarginalDesc *d, const void *a, const uint8_t *o
       first = false;
     }
   }
+  HIP_TRY(hipGetLastError());
+  return ARTN_OK;
+}
+
+} // extern "C"
+
+// In-place circuits: the runs of a circuit (include/artn.h: PLAN), their bases and every step's slot mask.
+struct PauliEvolveRunPlan {
+  int64_t first = 0, count = 0;
+  std::vector<uint64_t> basis; // reduced echelon, ascending pivots
+  std::vector<int> pivot;
+};
+struct PauliEvolvePlan {
+  PauliPlan pl;
+  std::vector<PauliEvolveRunPlan> runs;
+  std::vector<int32_t> run_of, slot_mask;
+  ArtnPauliEvolveInfo info = {};
+};
+
+// v reduced by the basis; when something is left, it joins (its highest bit is the pivot, cleared from every other vector)
+static void pauli_evolve_span_add(std::vector<uint64_t> &basis, std::vector<int> &pivot, uint64_t v) {
+  for (size_t j = 0; j < basis.size(); ++j)
+    if ((v >> pivot[j]) & 1) v ^= basis[j];
+  if (!v) return;
+  const int p = 63 - __builtin_clzll(v);
+  for (uint64_t &b : basis)
+    if ((b >> p) & 1) b ^= v;
+  basis.push_back(v), pivot.push_back(p);
+}
+
+static int pauli_evolve_plan(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_steps, int32_t max_rank, PauliEvolvePlan &ep) {
+  if (int rc = pauli_plan(d, ops, n_steps, ep.pl)) return rc;
+  const PauliPlan &pl = ep.pl;
+  const int lib_max = d->dtype == ARTN_C64 ? ARTN_PAULI_EVOLVE_MAX_RANK : ARTN_PAULI_EVOLVE_MAX_RANK - 1;
+  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
+  if (max_rank > lib_max)
+    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the maximum " + std::to_string(lib_max) + " of this dtype");
+  if (n_steps > INT32_MAX) return fail(ARTN_E_UNSUPPORTED, "too many steps in one circuit");
+  if (max_rank < 0) max_rank = lib_max - 1; // 64 KiB of LDS per workgroup
+  int tile_bits = 0;
+  while (((int64_t)1 << (ARTN_PAULI_TILE_BITS + tile_bits + 1)) <= pl.n) ++tile_bits;
+  const int cap = std::min<int>(max_rank, tile_bits);
+  const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
+  ep.run_of.assign(n_steps, 0), ep.slot_mask.assign(n_steps, 0);
+  PauliEvolveRunPlan cur;
+  auto close = [&]() {
+    // ascending pivots, then every step's slot mask: bit j = the step's xm_hi at pivot j (each pivot lies in one basis vector)
+    std::vector<size_t> idx(cur.basis.size());
+    for (size_t j = 0; j < idx.size(); ++j) idx[j] = j;
+    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return cur.pivot[x] < cur.pivot[y]; });
+    PauliEvolveRunPlan r = cur;
+    for (size_t j = 0; j < idx.size(); ++j) r.basis[j] = cur.basis[idx[j]], r.pivot[j] = cur.pivot[idx[j]];
+    for (int64_t k = r.first; k < r.first + r.count; ++k) {
+      int32_t m = 0;
+      for (size_t j = 0; j < r.pivot.size(); ++j) m |= (int32_t)((pl.xm[k] >> r.pivot[j]) & 1) << j;
+      ep.slot_mask[k] = m, ep.run_of[k] = (int32_t)ep.runs.size();
+    }
+    ep.runs.push_back(r);
+  };
+  for (int64_t k = 0; k < n_steps; ++k) {
+    const uint64_t hi = pl.xm[k] & ~in;
+    if (hi) {
+      std::vector<uint64_t> b = cur.basis;
+      std::vector<int> p = cur.pivot;
+      pauli_evolve_span_add(b, p, hi);
+      if ((int)b.size() > cap && !cur.basis.empty()) { // (a run always takes its first step with a high flip)
+        close();
+        cur = PauliEvolveRunPlan();
+        cur.first = k;
+        pauli_evolve_span_add(cur.basis, cur.pivot, hi);
+      } else {
+        cur.basis = b, cur.pivot = p;
+      }
+    }
+    ++cur.count;
+  }
+  close();
+  const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16, nr = (int64_t)ep.runs.size();
+  ep.info.n_runs = ep.info.n_launches = (int32_t)nr;
+  ep.info.max_rank = cap;
+  ep.info.table_bytes = (int64_t)sizeof(ArtnPauliEvolveHeader) + nr * (int64_t)sizeof(ArtnPauliEvolveRun) + n_steps * (int64_t)sizeof(ArtnPauliEvolveStep);
+  ep.info.bytes_read = ep.info.bytes_written = nr * pl.n * elem;
+  return ARTN_OK;
+}
+
+template <typename T, int R>
+static hipError_t pauli_evolve_launch_rank(T *a, long tiles, const ArtnPauliEvolveRun *run, const ArtnPauliEvolveStep *stp, hipStream_t st) {
+  const size_t lds = ((size_t)sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
+  if (hipError_t e = ensure_lds<artn_k_pauli_evolve<T, R>>(lds); e != hipSuccess) return e;
+  const long n_blocks = tiles >> R;
+  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_PAULI_EVOLVE_MAX_GRID));
+  hipLaunchKernelGGL((artn_k_pauli_evolve<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, a, n_blocks, run, stp);
+  return hipSuccess;
+}
+
+template <typename T>
+static hipError_t pauli_evolve_launch(const PauliEvolvePlan &ep, T *a, const void *table, hipStream_t st) {
+  const ArtnPauliEvolveRun *runs = (const ArtnPauliEvolveRun *)((const ArtnPauliEvolveHeader *)table + 1);
+  const ArtnPauliEvolveStep *stp = (const ArtnPauliEvolveStep *)(runs + ep.runs.size());
+  const int64_t n = ep.pl.n;
+  if (n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
+    hipLaunchKernelGGL(artn_k_pauli_evolve_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, a, (long)n, stp, (int)ep.pl.xm.size());
+    return hipSuccess;
+  }
+  const long tiles = (long)(n >> ARTN_PAULI_TILE_BITS);
+  for (size_t r = 0; r < ep.runs.size(); ++r) {
+    hipError_t e = hipErrorInvalidValue;
+    switch ((int)ep.runs[r].basis.size()) {
+    case 0: e = pauli_evolve_launch_rank<T, 0>(a, tiles, runs + r, stp, st); break;
+    case 1: e = pauli_evolve_launch_rank<T, 1>(a, tiles, runs + r, stp, st); break;
+    case 2: e = pauli_evolve_launch_rank<T, 2>(a, tiles, runs + r, stp, st); break;
+    case 3: e = pauli_evolve_launch_rank<T, 3>(a, tiles, runs + r, stp, st); break;
+    case 4:
+      if constexpr (sizeof(T) == 8) e = pauli_evolve_launch_rank<T, 4>(a, tiles, runs + r, stp, st);
+      break;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+extern "C" {
+
+int artn_pauli_evolve_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
+                            ArtnPauliEvolveInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run,
+                            int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot) {
+  if (!info) return fail(ARTN_E_INVALID, "null info");
+  if (!coeff) return fail(ARTN_E_INVALID, "null pointer");
+  PauliEvolvePlan ep;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
+  const PauliPlan &pl = ep.pl;
+  *info = ep.info;
+  if (xmask) std::copy(pl.xm.begin(), pl.xm.end(), xmask);
+  if (zmask) std::copy(pl.zm.begin(), pl.zm.end(), zmask);
+  if (n_y) std::copy(pl.ny.begin(), pl.ny.end(), n_y);
+  if (run) std::copy(ep.run_of.begin(), ep.run_of.end(), run);
+  if (slot_mask) std::copy(ep.slot_mask.begin(), ep.slot_mask.end(), slot_mask);
+  for (size_t r = 0; r < ep.runs.size(); ++r) {
+    const PauliEvolveRunPlan &rp = ep.runs[r];
+    if (run_rank) run_rank[r] = (int32_t)rp.basis.size();
+    for (size_t j = 0; j < ARTN_PAULI_EVOLVE_MAX_RANK; ++j) {
+      if (run_basis) run_basis[r * ARTN_PAULI_EVOLVE_MAX_RANK + j] = j < rp.basis.size() ? rp.basis[j] : 0;
+      if (run_pivot) run_pivot[r * ARTN_PAULI_EVOLVE_MAX_RANK + j] = j < rp.pivot.size() ? rp.pivot[j] : -1;
+    }
+  }
+  return ARTN_OK;
+}
+
+int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
+                           void *table, int64_t table_bytes) {
+  PauliEvolvePlan ep;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
+  if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ep.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_evolve_query reports");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve_pack needs an 8-byte aligned table");
+  const PauliPlan &pl = ep.pl;
+  const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
+  ArtnPauliEvolveHeader *h = (ArtnPauliEvolveHeader *)table;
+  ArtnPauliEvolveRun *runs = (ArtnPauliEvolveRun *)(h + 1);
+  ArtnPauliEvolveStep *stp = (ArtnPauliEvolveStep *)(runs + ep.runs.size());
+  *h = ArtnPauliEvolveHeader{(uint64_t)ep.runs.size(), (uint64_t)n_steps, (uint64_t)ep.info.max_rank, 0};
+  for (size_t r = 0; r < ep.runs.size(); ++r) {
+    const PauliEvolveRunPlan &rp = ep.runs[r];
+    ArtnPauliEvolveRun rec = {};
+    rec.first = (uint64_t)rp.first, rec.count = (uint64_t)rp.count, rec.rank = (uint64_t)rp.basis.size();
+    for (size_t j = 0; j < rp.basis.size(); ++j) rec.basis[j] = rp.basis[j], rec.pivot[j] = (uint64_t)rp.pivot[j];
+    runs[r] = rec;
+  }
+  for (int64_t k = 0; k < n_steps; ++k) {
+    // (below one tile the small kernel reads the whole xmask here: it has no bits above the tile)
+    stp[k] = ArtnPauliEvolveStep{pl.xm[k] & in, (uint64_t)ep.slot_mask[k], pl.zm[k], (uint64_t)pl.ny[k],
+                                 coeff[4 * k], coeff[4 * k + 1], coeff[4 * k + 2], coeff[4 * k + 3]};
+  }
+  return ARTN_OK;
+}
+
+int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, int64_t n_steps, int32_t max_rank, const void *table,
+                      int64_t table_bytes, void *stream) {
+  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
+  PauliEvolvePlan ep;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc; // (the coefficients are in the table)
+  if (!a || !table) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ep.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_evolve_query reports");
+  if (((uintptr_t)a & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve needs a 16-byte aligned array");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve needs an 8-byte aligned table");
+  hipStream_t st = (hipStream_t)stream;
+  if (d->dtype == ARTN_C64) HIP_TRY(pauli_evolve_launch(ep, (float2 *)a, table, st));
+  else HIP_TRY(pauli_evolve_launch(ep, (double2 *)a, table, st));
   HIP_TRY(hipGetLastError());
   return ARTN_OK;
 }

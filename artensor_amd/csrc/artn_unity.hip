@@ -20,4 +20,4 @@
 #endif
 #include "artn_born.hip"
 #include "artn_rdm.hip"
-#include "artn_pauli.hip"
+#include "artn_pauli.hip" // (artn_pauli_kernel.h, artn_pauli_apply_kernel.h, artn_pauli_evolve_kernel.h)

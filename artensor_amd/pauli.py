@@ -1,6 +1,7 @@
 """Expectation values of Pauli strings and of sums of them (Hamiltonians) on an amplitude tensor on the device (C ABI:
 artn_pauli_query, artn_pauli_expect), and the same operators APPLIED to the tensor: y = H a in one launch (artn_pauli_apply_query,
-artn_pauli_apply_pack, artn_pauli_apply).
+artn_pauli_apply_pack, artn_pauli_apply), and IN-PLACE circuits of steps a <- alpha a + beta P a -- rotations exp(-i theta P) among
+them -- fused into runs that read and write the state once (artn_pauli_evolve_query, artn_pauli_evolve_pack, artn_pauli_evolve).
 
 A Pauli string gives every dim of `amps` one of I, X, Y, Z -- X, Y and Z only on dims of extent 2, every other dim (a row
 dimension, an extent-1 dim) carries I.  It is written either as a `str` of length amps.dim() over "IXYZ" (any case; character d
@@ -21,7 +22,8 @@ from . import _native
 from .born import _DTYPES, _checked, norm2, overlap
 
 __all__ = ["pauli_ops", "pauli_info", "pauli_expectation", "pauli_sum_expectation", "pauli_apply_info", "PauliSumOperator",
-           "pauli_sum_apply", "pauli_apply", "pauli_rotate", "pauli_sum_variance"]
+           "pauli_sum_apply", "pauli_apply", "pauli_rotate", "pauli_sum_variance", "pauli_evolve_info", "PauliCircuit",
+           "pauli_evolve_", "pauli_rotate_", "pauli_apply_", "trotter_steps"]
 
 _CODES = {"I": 0, "X": 1, "Y": 2, "Z": 3}
 
@@ -274,3 +276,149 @@ def pauli_sum_variance(amps, terms):
     aha, na, _ = overlap(amps, y)
     e = aha.real / na
     return e, norm2(y) / na - e * e
+
+
+# ---- in-place circuits -------------------------------------------------------------------------------------------------------
+def _split_steps(steps, n_dims):
+    """([n_steps, 4] float64 alpha, beta; uint8 ops) of steps = [(theta, string) | (alpha, beta, string), ...]."""
+    steps = list(steps)
+    if not steps:
+        raise ValueError("at least one step is needed")
+    coeff, strings = np.zeros((len(steps), 4), dtype=np.float64), []
+    for k, step in enumerate(steps):
+        if not isinstance(step, (tuple, list)) or len(step) not in (2, 3):
+            raise ValueError(f"step {k}: (theta, string) or (alpha, beta, string) expected, got {step!r}")
+        if len(step) == 2:
+            theta = float(step[0])
+            coeff[k] = (np.cos(theta), 0.0, 0.0, -np.sin(theta))
+        else:
+            alpha, beta = complex(step[0]), complex(step[1])
+            coeff[k] = (alpha.real, alpha.imag, beta.real, beta.imag)
+        strings.append(step[-1])
+    ops, _ = pauli_ops(strings, n_dims)
+    return np.ascontiguousarray(coeff), ops
+
+
+def _max_rank(max_rank):
+    return -1 if max_rank is None else int(max_rank)
+
+
+def _evolve_query(d, ops, coeff, max_rank, arrays=False):
+    n = ops.shape[0]
+    info = _native.ArtnPauliEvolveInfo()
+    if arrays:
+        xm, zm = (np.zeros(n, dtype=np.uint64) for _ in range(2))
+        ny, run, slot, rank = (np.zeros(n, dtype=np.int32) for _ in range(4))
+        basis = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.uint64)
+        pivot = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.int32)
+        out = (xm, zm, ny, run, slot, rank, basis, pivot)
+        ptrs = [_ptr(x) for x in out]
+    else:
+        out, ptrs = (), [None] * 8
+    _native.check(_native.lib().artn_pauli_evolve_query(ctypes.byref(d), _ptr(ops), _ptr(coeff), n, max_rank, ctypes.byref(info), *ptrs))
+    return (info,) + out
+
+
+def pauli_evolve_info(shape, strides, steps, dtype=torch.complex64, max_rank=None):
+    """Host-only: how a circuit of steps = [(theta, string) | (alpha, beta, string), ...] is cut into runs.  Per step: xmask, zmask,
+    n_y, alpha, beta (complex), run and slot_mask.  Per run: run_rank, run_basis (memory-bit masks, ascending pivots) and
+    run_pivot.  n_runs = n_launches, the effective max_rank, table_bytes, bytes_read = bytes_written = n_runs * bytes of the
+    state."""
+    if dtype not in _DTYPES:
+        raise TypeError(f"pauli_evolve_info: complex64 or complex128 expected, got {dtype}")
+    coeff, ops = _split_steps(steps, len(shape))
+    info, xm, zm, ny, run, slot, rank, basis, pivot = _evolve_query(_desc(shape, strides, dtype), ops, coeff, _max_rank(max_rank),
+                                                                    arrays=True)
+    nr = info.n_runs
+    ranks = [int(v) for v in rank[:nr]]
+    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny],
+            "alpha": [complex(c[0], c[1]) for c in coeff], "beta": [complex(c[2], c[3]) for c in coeff],
+            "run": [int(v) for v in run], "slot_mask": [int(v) for v in slot], "n_runs": nr, "n_launches": info.n_launches,
+            "max_rank": info.max_rank, "run_rank": ranks,
+            "run_basis": [[int(v) for v in basis[r, :ranks[r]]] for r in range(nr)],
+            "run_pivot": [[int(v) for v in pivot[r, :ranks[r]]] for r in range(nr)],
+            "table_bytes": info.table_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written}
+
+
+def _evolve_pack(d, ops, coeff, max_rank):
+    """The circuit table (include/artn.h) as a uint8 numpy array."""
+    info = _evolve_query(d, ops, coeff, max_rank)[0]
+    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
+    _native.check(_native.lib().artn_pauli_evolve_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], max_rank, _ptr(table),
+                                                       info.table_bytes))
+    return table.view(np.uint8), info
+
+
+class PauliCircuit:
+    """An ordered list of steps a <- alpha a + beta P a for tensors of one layout: steps = [(theta, string), ...] for the rotation
+    exp(-i theta P) or (alpha, beta, string) for the general step.  Validates, cuts the runs, packs the table and copies it to
+    `device` once; circ(amps) then updates amps IN PLACE with one launch per run and returns it.  max_rank: a run holds blocks of
+    up to 2^max_rank tiles of 2^10 elements in LDS (None: 64 KiB per workgroup; 0: one launch per step with a flip above the tile)."""
+
+    def __init__(self, shape, strides, dtype, steps, device, max_rank=None):
+        if dtype not in _DTYPES:
+            raise TypeError(f"PauliCircuit: complex64 or complex128 expected, got {dtype}")
+        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"PauliCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        coeff, self._ops = _split_steps(steps, len(self.shape))
+        self._d = _desc(self.shape, self.strides, dtype)
+        self._max_rank = _max_rank(max_rank)
+        table, info = _evolve_pack(self._d, self._ops, coeff, self._max_rank)
+        self.n_steps, self.n_runs, self.max_rank, self.table_bytes = self._ops.shape[0], info.n_runs, info.max_rank, info.table_bytes
+        self._table = torch.from_numpy(table).to(self.device)
+
+    def __call__(self, amps):
+        what = "pauli.PauliCircuit"
+        _checked(amps, what)
+        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
+            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
+                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
+        if amps.device != self._table.device:
+            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        with torch.cuda.device(amps.device):
+            _native.check(_native.lib().artn_pauli_evolve(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_steps,
+                                                          self._max_rank, self._table.data_ptr(), self.table_bytes,
+                                                          _native.current_stream_ptr(amps.device)))
+        return amps
+
+
+def pauli_evolve_(amps, steps, max_rank=None):
+    """The circuit `steps` (see PauliCircuit) applied to amps in place; returns amps."""
+    _checked(amps, "pauli.pauli_evolve_")
+    return PauliCircuit(amps.shape, amps.stride(), amps.dtype, steps, amps.device, max_rank)(amps)
+
+
+def pauli_rotate_(amps, string, theta):
+    """amps <- exp(-i theta P) amps in place: one launch, no second buffer."""
+    _checked(amps, "pauli.pauli_rotate_")
+    return PauliCircuit(amps.shape, amps.stride(), amps.dtype, [(float(theta), string)], amps.device)(amps)
+
+
+def pauli_apply_(amps, string):
+    """amps <- P amps in place: an exact signed permutation."""
+    _checked(amps, "pauli.pauli_apply_")
+    return PauliCircuit(amps.shape, amps.stride(), amps.dtype, [(0.0, 1.0, string)], amps.device)(amps)
+
+
+def trotter_steps(terms, dt, order=1):
+    """Rotation list of one Trotter step of exp(-i dt H), H = sum_k c_k P_k with REAL c_k, terms = [(c_k, string_k), ...]: order 1
+    is exp(-i dt c_K P_K) ... exp(-i dt c_1 P_1) as [(dt c_1, P_1), ..., (dt c_K, P_K)]; order 2 the symmetric product, half
+    angles up to the last term, its full angle once (the two middle factors merged), then the half angles back: 2 K - 1 steps."""
+    terms = list(terms)
+    if not terms:
+        raise ValueError("at least one term is needed")
+    if order not in (1, 2):
+        raise ValueError(f"trotter_steps: order 1 or 2, got {order!r}")
+    coeffs = []
+    for c, _ in terms:
+        c = complex(c)
+        if c.imag != 0.0:
+            raise ValueError("trotter_steps takes real coefficients (a Hermitian sum)")
+        coeffs.append(c.real)
+    dt = float(dt)
+    if order == 1:
+        return [(dt * c, p) for c, (_, p) in zip(coeffs, terms)]
+    half = [(0.5 * dt * c, p) for c, (_, p) in zip(coeffs[:-1], terms[:-1])]
+    return half + [(dt * coeffs[-1], terms[-1][1])] + half[::-1]

@@ -433,6 +433,80 @@ int artn_pauli_apply_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const d
 int artn_pauli_apply(const ArtnMarginalDesc *d, const void *a, void *y, const uint8_t *ops, int64_t n_terms, const void *table,
                      int64_t table_bytes, void *stream);
 
+/*
+ * In-place circuits of Pauli steps (additive to ABI 9: look the symbols up before calling).  A CIRCUIT is an ordered list of
+ * n_steps STEPS; step k replaces the state by alpha_k a + beta_k P_k a, P_k a Pauli string (`ops` [n_steps][n_dims] as above),
+ * `coeff` float64 [n_steps][4] = Re alpha, Im alpha, Re beta, Im beta.  exp(-i theta P) is (cos theta, -i sin theta), P itself
+ * (0, 1), a projector (I +- P) / 2 is (1/2, +-1/2).  Steps are never reordered; `a` is updated in place in its own layout.
+ * Descriptor, masks, checks and refusals are those of artn_pauli_query.
+ *
+ * PLAN.  xmask = xm_lo (bits 0..9, inside a tile of 2^10 elements) + xm_hi.  The circuit is cut greedily, in order, into RUNS:
+ * a run is extended while the rank over GF(2) of the xm_hi of its steps stays at or below max_rank (a step with xm_hi = 0 never
+ * ends a run; a run always takes its first step with xm_hi != 0, so max_rank = 0 gives one run per such step).  A run of rank r
+ * is ONE launch that reads and writes the state once: with b_0 .. b_{r-1} the reduced-echelon basis of the span in ascending
+ * order of the pivots (pivot p_j is set in b_j and in no other b), the tiles are split into BLOCKS of 2^r tiles, the orbits of
+ * the span.  Block q (0 <= q < tiles >> r) has the representative tile whose index is q with a 0 inserted at every pivot (bit
+ * p_j - 10 of the tile index), ascending; SLOT s of the block is the tile (representative << 10 ^ XOR of b_j over the bits j of
+ * s) >> 10.  A workgroup holds the 2^r tiles of a block together and applies the run's steps to it; step k pairs slot s with slot
+ * s ^ m_k, its SLOT MASK: xm_hi = XOR of b_j over the bits j of m_k.
+ * max_rank: -1 selects the default, 64 KiB of LDS per workgroup (3 for complex64, 2 for complex128); the maximum is
+ * ARTN_PAULI_EVOLVE_MAX_RANK for complex64 and one less for complex128 (128 KiB); more is ARTN_E_UNSUPPORTED, below -1
+ * ARTN_E_INVALID.  States below 2^10 elements: one run, one launch, whatever max_rank.
+ *
+ * ARITHMETIC of a step, for every element i with partner j = i ^ xmask and the sign s = (-1)^popcount(i & zmask):
+ *     b = s * (-i)^n_y * a[j]   (sign changes and a swap of the components: exact)
+ *     Re new = Re alpha * Re a[i] - Im alpha * Im a[i] + Re beta * Re b - Im beta * Im b, and Im new likewise,
+ * operands converted to float64, the four products accumulated by fma from the last one to the first, a product whose coefficient
+ * component is exactly 0 left out, one rounding of each component to the dtype.  Between steps the state is held in the dtype, so
+ * the result does not depend on where the runs are cut, bit for bit; (1, 0) leaves finite data unchanged bit for bit and (0, 1)
+ * is an exact signed permutation.  No atomics.
+ *
+ * TABLE (what artn_pauli_evolve_pack writes and the kernels read; 8-byte little-endian fields):
+ *     ArtnPauliEvolveHeader   32 bytes     n_runs, n_steps, max_rank (the effective one), 0
+ *     n_runs x ArtnPauliEvolveRun   96 bytes each: first, count (its steps are first .. first + count - 1), rank, 0,
+ *                                   basis[4] (memory-bit masks, 0 beyond the rank), pivot[4] (memory bit numbers)
+ *     n_steps x ArtnPauliEvolveStep 64 bytes each, in circuit order: xm_lo, slot_mask, zmask, n_y, then Re alpha, Im alpha,
+ *                                   Re beta, Im beta as float64
+ * table_bytes = 32 + 96 * n_runs + 64 * n_steps.
+ */
+#define ARTN_PAULI_EVOLVE_MAX_RANK 4
+typedef struct ArtnPauliEvolveHeader {
+  uint64_t n_runs, n_steps, max_rank, reserved;
+} ArtnPauliEvolveHeader;
+typedef struct ArtnPauliEvolveRun {
+  uint64_t first, count, rank, reserved;
+  uint64_t basis[ARTN_PAULI_EVOLVE_MAX_RANK];
+  uint64_t pivot[ARTN_PAULI_EVOLVE_MAX_RANK];
+} ArtnPauliEvolveRun;
+typedef struct ArtnPauliEvolveStep {
+  uint64_t xm_lo, slot_mask, zmask, n_y;
+  double alpha_re, alpha_im, beta_re, beta_im;
+} ArtnPauliEvolveStep;
+typedef struct ArtnPauliEvolveInfo {
+  int32_t n_runs;
+  int32_t n_launches;    /* = n_runs                                               */
+  int32_t max_rank;      /* the effective one: the request or the default, capped by log2 of the number of tiles */
+  int32_t reserved;
+  int64_t table_bytes;
+  int64_t bytes_read;    /* n_runs * n * element size                              */
+  int64_t bytes_written; /* the same                                               */
+} ArtnPauliEvolveInfo;
+/* Host-only: validates, translates and cuts the runs.  Per step (n_steps entries each, any may be NULL): xmask, zmask, n_y, run
+ * (the run of the step) and slot_mask.  Per run (room for n_steps entries each, n_runs are written; any may be NULL): run_rank,
+ * run_basis ([.][4] memory-bit masks) and run_pivot ([.][4] bit numbers, -1 beyond the rank). */
+int artn_pauli_evolve_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
+                            ArtnPauliEvolveInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run,
+                            int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query with the same max_rank). */
+int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
+                           void *table, int64_t table_bytes);
+/* The circuit on `a`, in place: one launch per run on `stream`, in order.  `table` is DEVICE memory holding what
+ * artn_pauli_evolve_pack wrote for the same descriptor, ops, n_steps and max_rank (8-byte aligned; a table_bytes below the query's
+ * is ARTN_E_INVALID); `a` is 16-byte aligned (ARTN_E_UNSUPPORTED otherwise).  No allocation, copy or synchronisation.
+ * ARTN_E_NODEVICE without a device. */
+int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, int64_t n_steps, int32_t max_rank, const void *table,
+                      int64_t table_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
