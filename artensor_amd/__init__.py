@@ -78,6 +78,16 @@ from .pauli import (  # noqa: F401
     pauli_sum_variance,
     trotter_steps,
 )
+from . import gates  # noqa: F401
+from .gates import (  # noqa: F401
+    GateCircuit,
+    apply_gate_,
+    apply_gates_,
+    gate_circuit_info,
+    gates_from_bonds,
+    merge_gates,
+    run_circuit,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

@@ -172,8 +172,9 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_pauli_small(const T 
   if (threadIdx.x <= NT) partial[threadIdx.x] = red[0][threadIdx.x];
 }
 
-// partial: n_partial rows of nv doubles (nv - 1 term slots, then sum |a|^2)
-__global__ __launch_bounds__(64) void artn_k_pauli_finish(const double *__restrict__ partial, int n_partial, int nv, ArtnPauliFinish f,
+// partial: n_partial rows of nv doubles (nv - 1 term slots, then sum |a|^2)  (static, as the non-template kernels of
+// artn_born_kernel.h: this header is included by more than one translation unit)
+static __global__ __launch_bounds__(64) void artn_k_pauli_finish(const double *__restrict__ partial, int n_partial, int nv, ArtnPauliFinish f,
                                                           double *__restrict__ out) {
   const int q = threadIdx.x;
   const bool term = q < f.nt, norm = q == nv - 1 && f.norm_index >= 0;

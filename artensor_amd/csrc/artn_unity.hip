@@ -21,3 +21,4 @@
 #include "artn_born.hip"
 #include "artn_rdm.hip"
 #include "artn_pauli.hip" // (artn_pauli_kernel.h, artn_pauli_apply_kernel.h, artn_pauli_evolve_kernel.h)
+#include "artn_gates.hip" // (artn_gates_kernel.h)

@@ -507,6 +507,92 @@ int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const 
 int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, int64_t n_steps, int32_t max_rank, const void *table,
                       int64_t table_bytes, void *stream);
 
+/*
+ * In-place circuits of dense one- and two-qubit gates (additive to ABI 9: look the symbols up before calling).  A CIRCUIT is an
+ * ordered list of n_gates GATES; gate g acts on k[g] (1 or 2) distinct dimensions of extent 2, dims[g][0 .. k-1] (dims is int32
+ * [n_gates][2]; the second entry of a one-qubit gate is ignored), with the matrix mat[g] (float64 [n_gates][32]: the 2^k x 2^k
+ * matrix row-major, Re and Im interleaved, in the first 2 * 4^k entries).  Any matrix, unitary or not.  The convention is that of
+ * artn_rdm: the FIRST listed dimension is the most significant digit of the row and column index,
+ *     new[.., i0, .., i1, ..] = sum_{j0, j1} U[2 i0 + i1][2 j0 + j1] a[.., j0, .., j1, ..].
+ * Gates are never reordered; `a` is updated in place in its own layout.  Descriptor and density checks are those of
+ * artn_pauli_query (keep[] ignored).  ARTN_E_UNSUPPORTED: k outside {1, 2} (and the refusals of artn_pauli_evolve_query);
+ * ARTN_E_INVALID: a dimension out of range, repeated or of extent other than 2, a matrix entry that is not finite, n_gates < 1.
+ *
+ * PLAN.  A target dimension of stride 2^b is memory bit b: bits 0..9 lie inside a tile of 2^10 elements, bits >= 10 are HIGH.
+ * The circuit is cut greedily, in order, into RUNS: a run is extended while the distinct high target bits of its gates number at
+ * most max_rank (a gate without a high bit never ends a run; a run always takes its first gate with a high bit, so a two-qubit
+ * gate on two high bits opens a run of rank 2 when max_rank is 0 or 1 -- the unfused form; such a run still takes gates
+ * whose high bits are among its own, which need no larger block, and ends at the first gate that brings a new one).  A run of rank r is ONE
+ * launch that reads and writes the state once.  Its PIVOTS p_0 < .. < p_{r-1} are its high target bits; this is the block
+ * structure of artn_pauli_evolve with the unit vectors 1 << p_j as basis: block q (0 <= q < tiles >> r) has the representative
+ * tile whose index is q with a 0 inserted at every bit p_j - 10, ascending, and SLOT s of the block is the representative with
+ * bit p_j - 10 set for every bit j of s.  A gate's SLOT MASK has bit j set when p_j is one of its targets.
+ * max_rank: -1 selects the default, 64 KiB of LDS per workgroup (3 for complex64, 2 for complex128); the maximum is
+ * ARTN_GATES_MAX_RANK for complex64 and one less for complex128; more is ARTN_E_UNSUPPORTED, below -1 ARTN_E_INVALID.  The
+ * effective value is capped by log2 of the number of tiles.  States below 2^10 elements: one run, one launch.
+ * A gate is THREAD-LOCAL (no LDS traffic, no barrier) when its matrix is diagonal or all its targets lie in memory bits 0..1.
+ *
+ * ARITHMETIC of a gate.  With T_0 the LAST listed target and T_1 the first one of a two-qubit gate, the row of element i is
+ * r = bit T_0 of i + 2 * bit T_1 of i, and
+ *     new a[i] = sum over d = 2^k - 1 down to 0 of U[r][r ^ d] * a[i with T_0 flipped if d & 1, T_1 flipped if d & 2]
+ * (the element itself comes last).  Operands are converted to float64; a term adds, by fma into accumulators that start at -0.0,
+ * first the two products with Im U (-Im U Im a to the real part, Im U Re a to the imaginary part), then the two with Re U; the
+ * two products of a coefficient component that is exactly 0 are left out; one rounding of each component to the dtype.  Between
+ * gates the state is held in the dtype, so the result does not depend on where the runs are cut, bit for bit; the identity leaves
+ * finite data unchanged bit for bit and a matrix with one entry of {1, -1, i, -i} per row and column is an exact signed
+ * permutation.  No atomics.
+ *
+ * TABLE (what artn_gates_pack writes and the kernels read; 8-byte little-endian fields):
+ *     ArtnGatesHeader         32 bytes    n_runs, n_gates, max_rank (the effective one), 0
+ *     n_runs x ArtnGatesRun   64 bytes each: first, count (its gates are first .. first + count - 1), rank, 0,
+ *                             pivot[4] (memory bit numbers, ascending; 0 beyond the rank)
+ *     n_gates x ArtnGatesGate 320 bytes each, in circuit order: k, flags (ARTN_GATE_DIAGONAL | ARTN_GATE_LOCAL), then for
+ *                             T_0 and T_1 in this order (all 0 for the absent T_1 of a one-qubit gate): bit[2] the memory bit,
+ *                             slot[2] the one bit of the slot mask (0: not high), lo[2] the flip mask inside the tile
+ *                             (1 << bit below 10, else 0); then m[4][4][2]: U[r][c] as float64 (Re, Im) at m[r][c], rows
+ *                             and columns beyond 2^k zero
+ * table_bytes = 32 + 64 * n_runs + 320 * n_gates.
+ */
+#define ARTN_GATES_MAX_RANK 4
+#define ARTN_GATE_DIAGONAL 1
+#define ARTN_GATE_LOCAL 2
+typedef struct ArtnGatesHeader {
+  uint64_t n_runs, n_gates, max_rank, reserved;
+} ArtnGatesHeader;
+typedef struct ArtnGatesRun {
+  uint64_t first, count, rank, reserved;
+  uint64_t pivot[ARTN_GATES_MAX_RANK];
+} ArtnGatesRun;
+typedef struct ArtnGatesGate {
+  uint64_t k, flags;
+  uint64_t bit[2], slot[2], lo[2];
+  double m[4][4][2];
+} ArtnGatesGate;
+typedef struct ArtnGatesInfo {
+  int32_t n_runs;
+  int32_t n_launches;    /* = n_runs                                               */
+  int32_t max_rank;      /* the effective one: the request or the default, capped by log2 of the number of tiles */
+  int32_t reserved;
+  int64_t table_bytes;
+  int64_t bytes_read;    /* n_runs * n * element size                              */
+  int64_t bytes_written; /* the same                                               */
+} ArtnGatesInfo;
+/* Host-only: validates, translates and cuts the runs.  Per gate (n_gates entries each, any may be NULL): bits ([.][2] the memory
+ * bits in the order the dims are listed, -1 for the absent second one), run, slot_mask and local (1: thread-local).  Per run
+ * (room for n_gates entries each, n_runs are written; any may be NULL): run_rank and run_pivot ([.][4], -1 beyond the rank). */
+int artn_gates_query(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat, int64_t n_gates,
+                     int32_t max_rank, ArtnGatesInfo *info, int32_t *bits, int32_t *run, int32_t *slot_mask, int32_t *local,
+                     int32_t *run_rank, int32_t *run_pivot);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query with the same max_rank). */
+int artn_gates_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat, int64_t n_gates,
+                    int32_t max_rank, void *table, int64_t table_bytes);
+/* The circuit on `a`, in place: one launch per run on `stream`, in order.  `table` is DEVICE memory holding what artn_gates_pack
+ * wrote for the same descriptor, k, dims, n_gates and max_rank (8-byte aligned; a table_bytes below the query's is
+ * ARTN_E_INVALID); `mat` may be NULL here (the matrices are in the table); `a` is 16-byte aligned (ARTN_E_UNSUPPORTED otherwise).
+ * No allocation, copy or synchronisation.  ARTN_E_NODEVICE without a device. */
+int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const int32_t *dims, const double *mat, int64_t n_gates,
+                     int32_t max_rank, const void *table, int64_t table_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
