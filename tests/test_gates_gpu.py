@@ -300,7 +300,55 @@ def test_a_rotation_as_a_gate_is_pauli_rotate(kind):
         check(got, oracle(a, [gate]), a, [gate], kind, f"exp(-i theta X_{q}) {kind} against numpy")
 
 
-# ---- 8. argument checks -------------------------------------------------------------------------------------------------------
+# ---- 8. states below one tile -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["c64", "c128"])
+@pytest.mark.parametrize("nq", [1, 2, 5])
+def test_small_states(nq, kind):
+    rng = np.random.default_rng(70 + nq)
+    a = crand(rng, (2,) * nq, kind)
+    base = gpu(a)
+    if nq == 1:
+        gates = [(random_unitary(rng, 2), (0,)), (ASYM1, (0,)), (S, (-1,)), (random_unitary(rng, 2), (0,))]
+    else:
+        gates = random_circuit(rng, nq, 12) + [(ASYM2, (0, nq - 1)), (ASYM2, (nq - 1, 0)), (ASYM1, (nq - 1,)), (CNOT, (1, 0))]
+        assert any(len(d) == 2 and d[0] < d[1] for _, d in gates) and any(len(d) == 2 and d[0] > d[1] for _, d in gates)
+    info = A.gate_circuit_info(base.shape, base.stride(), gates, base.dtype)
+    assert info["n_runs"] == 1 and info["run_rank"] == [0] and info["max_rank"] == 0
+    for g, gate in enumerate(gates[-4:]):                                  # each alone, then the circuit
+        t = base.clone()
+        A.apply_gate_(t, *gate)
+        check(t, oracle(a, [gate]), a, [gate], kind, f"[2]*{nq} {kind} gate {g} on dims {gate[1]}")
+    t = base.clone()
+    assert A.apply_gates_(t, gates) is t
+    check(t, oracle(a, gates), a, gates, kind, f"[2]*{nq} {kind} {len(gates)} gates")
+
+
+# ---- 9. layouts that are not [2]*n --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["c64", "c128"])
+@pytest.mark.parametrize("layout", ["extents 4 and 8", "extent 1"])
+def test_non_qubit_layouts(layout, kind):
+    rng = np.random.default_rng(9)
+    if layout == "extents 4 and 8":
+        shape, perm = (4, 2, 2, 2, 8, 2, 2, 2, 2), (1, 0, 3, 2, 5, 4, 7, 6, 8)
+    else:
+        shape, perm = (1, 2, 2, 1) + (2,) * 10 + (1,), (0, 5, 2, 3, 1, 4, 6, 7, 8, 9, 10, 11, 13, 12, 14)
+    a = crand(rng, shape, kind)
+    t = gpu(a).permute(perm)
+    logical = a.transpose(perm)
+    twos = [d for d, e in enumerate(t.shape) if e == 2]
+    assert len(twos) == (7 if layout == "extents 4 and 8" else 12) and not t.is_contiguous()
+    gates = [(ASYM1, (d,)) for d in twos] + [(ASYM2, (d, e)) for d, e in zip(twos, twos[1:] + twos[:1])] \
+        + [(ASYM2, (twos[-1], twos[0])), (random_unitary(rng, 4), (twos[len(twos) // 2], twos[1]))]
+    assert {d for _, dims in gates for d in dims} == set(twos)
+    info = A.gate_circuit_info(t.shape, t.stride(), gates, t.dtype)
+    assert info["bits"] == [tuple(int(t.stride(d)).bit_length() - 1 for d in dims) for _, dims in gates]   # extent 2: stride = 2^bit
+    assert all(t.stride(d) == 1 << b for (_, dims), bits in zip(gates, info["bits"]) for d, b in zip(dims, bits))
+    strides = t.stride()
+    assert A.apply_gates_(t, gates) is t and t.stride() == strides
+    check(t, oracle(logical, gates), a, gates, kind, f"{layout} {kind}: {len(gates)} gates on dims {twos}")
+
+
+# ---- 10. argument checks ------------------------------------------------------------------------------------------------------
 def test_argument_checks():
     t = gpu(np.zeros((2,) * 4, dtype=np.complex64))
     gates = [(ASYM1, (0,)), (ASYM2, (3, 1))]
