@@ -88,6 +88,15 @@ from .gates import (  # noqa: F401
     merge_gates,
     run_circuit,
 )
+from . import wide_gates  # noqa: F401
+from .wide_gates import (  # noqa: F401
+    FusedCircuit,
+    WideGate,
+    apply_circuit_,
+    apply_wide_gate_,
+    fuse_gates,
+    wide_gate_info,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

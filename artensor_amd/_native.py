@@ -160,6 +160,26 @@ class ArtnGatesInfo(ctypes.Structure):
 GATES_MAX_RANK = 4
 GATE_DIAGONAL, GATE_LOCAL = 1, 2
 
+
+class ArtnWgateInfo(ctypes.Structure):
+    _fields_ = [
+        ("k", ctypes.c_int32),
+        ("tile_bits", ctypes.c_int32),
+        ("diagonal", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("n_tiles", ctypes.c_int64),
+        ("segment", ctypes.c_int64),
+        ("lds_bytes", ctypes.c_int64),
+        ("table_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
+WGATE_MAX_K = 5
+WGATE_TILE_BITS = {ARTN_C64: 12, ARTN_C128: 11}
+WGATE_TABLE_HEADER_BYTES = 480
+
 _lib = None
 _lock = threading.Lock()
 
@@ -250,6 +270,13 @@ _EXPORTS = {
     "artn_gates_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_void_p]),
+    # additive to ABI 9 as well: one dense gate on one to five qubits, in place (has("artn_wgate_apply"))
+    "artn_wgate_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.POINTER(ArtnWgateInfo), ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_wgate_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_int64]),
+    "artn_wgate_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

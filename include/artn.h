@@ -593,6 +593,81 @@ int artn_gates_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *
 int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const int32_t *dims, const double *mat, int64_t n_gates,
                      int32_t max_rank, const void *table, int64_t table_bytes, void *stream);
 
+/*
+ * ONE dense gate on one to five qubits, in place, in one launch (additive to ABI 9: look the symbols up before calling).  The
+ * gate acts on k (1..5) distinct dimensions of extent 2, dims[0 .. k-1], with the matrix mat (float64 [2 * 4^k]: the 2^k x 2^k
+ * matrix row-major, Re and Im interleaved).  Any matrix, unitary or not.  The convention is that of artn_gates_*: the FIRST
+ * listed dimension is the most significant digit of the row and column index,
+ *     new[.., i0, .., i_{k-1}, ..] = sum_j U[(i0 .. i_{k-1})_2][(j0 .. j_{k-1})_2] a[.., j0, .., j_{k-1}, ..].
+ * Descriptor and density checks are those of artn_gates_query.  ARTN_E_UNSUPPORTED: k outside 1..5 (and the layout and dtype
+ * refusals of artn_gates_query); ARTN_E_INVALID: k above the number of memory bits of the state, a dimension out of range,
+ * repeated or of extent other than 2, a matrix entry that is not finite, a null pointer.
+ *
+ * PLAN.  A target dimension of stride 2^b is memory bit b.  The state is cut into TILES of 2^TB elements, TB =
+ * ARTN_WGATE_TILE_BITS_C64 / _C128 (32 KiB of LDS), or the whole state when it is smaller.  The TILE BITS are the k target bits
+ * and the TB - k lowest memory bits that are not targets; tile-local bit j is the j-th tile bit in ascending order.  Memory bits
+ * 0 .. TB-k-1 always lie in the tile, so a tile is made of contiguous SEGMENTS of `segment` >= 2^(TB-k) elements (segment = 2^s,
+ * s the number of leading tile bits j that are memory bit j); the tile bits above s are all targets, the HIGH targets.  Tile q
+ * starts at the element whose index is q << s with a 0 inserted at every high target bit, ascending.
+ *
+ * IN LDS an element of the tile with row c (bit i of c = the bit of the i-th target counted from the LAST listed one) and
+ * GROUP g (its TB - k non-target tile bits, compacted) lies at index ((c << (TB-k)) | g) ^ sw(c), sw(c) = XOR of swizzle[i] over
+ * the set bits i of c.  A workgroup loads the tile (16-byte global loads), forms every output from the 2^k members of its group
+ * read from LDS, writes the outputs back to LDS once every thread has read, and stores the tile (16-byte global stores): one
+ * read and one write of the state.  The swizzle moves the targets among the lowest six tile-local bits to LDS index bits of
+ * their own, so that the consecutive elements a wavefront loads or stores spread over the LDS banks whatever the targets.
+ *
+ * ARITHMETIC: that of artn_gates_apply, stated for any k.  For output row r the accumulators of both components start at -0.0;
+ * terms come in the order d = 2^k - 1 .. 0 with column c = r ^ d; a term adds, by fma in float64, first the two products with
+ * Im U (-Im U Im a to the real part, Im U Re a to the imaginary part), then the two with Re U; the two products of a coefficient
+ * component that is exactly 0 are left out; one rounding of each component to the dtype.  So the identity leaves finite data
+ * unchanged bit for bit, a matrix with one entry of {1, -1, i, -i} per row and column is an exact signed permutation, a gate with
+ * k <= 2 gives what artn_gates_apply gives bit for bit, and so does a one- or two-qubit matrix kron identities.  No atomics.
+ *
+ * TABLE (what artn_wgate_pack writes and the kernel reads; 8-byte little-endian fields): ArtnWgateTable, 480 bytes, then the
+ * matrix as float64 (Re, Im), row-major, 16 * 4^k bytes.  table_bytes = 480 + 16 * 4^k.
+ */
+#define ARTN_WGATE_MAX_K 5
+#define ARTN_WGATE_TILE_BITS_C64 12
+#define ARTN_WGATE_TILE_BITS_C128 11
+#define ARTN_WGATE_ROWS 8 /* a thread forms up to this many rows of a group; block_mask is over blocks of ROWS x ROWS entries */
+typedef struct ArtnWgateTable {
+  uint64_t k, tile_bits, n_tiles, segment;
+  uint64_t flags;      /* ARTN_GATE_DIAGONAL                                                                        */
+  uint64_t group_bits; /* tile_bits - k                                                                              */
+  uint64_t n_high;     /* tile bits at or above log2(segment): all targets                                           */
+  uint64_t block_mask; /* bit rb * nb + cb (nb = max(1, 2^k / ROWS)): block (rb, cb) of the matrix has a non-zero    */
+  uint64_t target_bit[ARTN_WGATE_MAX_K]; /* the memory bits of the targets in the order listed                       */
+  uint64_t target_pos[ARTN_WGATE_MAX_K]; /* their tile-local positions, same order                                   */
+  uint64_t high_bit[ARTN_WGATE_MAX_K];   /* the high targets' memory bits, ascending (0 beyond n_high)                */
+  uint64_t swizzle[ARTN_WGATE_MAX_K];    /* per ROW bit i (the i-th target from the last listed one), below 2^group_bits */
+  uint64_t mem_col[16];                  /* per tile-local bit j: 1 << its memory bit (0 beyond tile_bits): the bit scatter */
+  uint64_t lds_col[16];                  /* per tile-local bit j: what it contributes (XOR) to the LDS index             */
+} ArtnWgateTable;
+typedef struct ArtnWgateInfo {
+  int32_t k;
+  int32_t tile_bits;   /* TB, or log2 of the state when that is smaller          */
+  int32_t diagonal;    /* 1: every off-diagonal entry is exactly 0               */
+  int32_t reserved;
+  int64_t n_tiles;     /* n_tiles << tile_bits = elements of the state           */
+  int64_t segment;     /* elements of a contiguous segment of a tile             */
+  int64_t lds_bytes;
+  int64_t table_bytes;
+  int64_t bytes_read;  /* the state                                              */
+  int64_t bytes_written;
+} ArtnWgateInfo;
+/* Host-only: validates and plans.  target_bits (k entries, the order listed) and tile_bits (info->tile_bits entries, ascending;
+ * room for 12) may be NULL. */
+int artn_wgate_query(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const double *mat, ArtnWgateInfo *info,
+                     int32_t *target_bits, int32_t *tile_bits);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_wgate_pack(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const double *mat, void *table, int64_t table_bytes);
+/* The gate on `a`, in place: ONE launch on `stream`.  `table` is DEVICE memory holding what artn_wgate_pack wrote for the same
+ * descriptor, k and dims (8-byte aligned; a table_bytes below the query's is ARTN_E_INVALID); `a` is 16-byte aligned
+ * (ARTN_E_UNSUPPORTED otherwise).  No allocation, copy or synchronisation.  ARTN_E_NODEVICE without a device. */
+int artn_wgate_apply(const ArtnMarginalDesc *d, void *a, int32_t k, const int32_t *dims, const void *table, int64_t table_bytes,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
