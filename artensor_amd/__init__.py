@@ -97,6 +97,16 @@ from .wide_gates import (  # noqa: F401
     fuse_gates,
     wide_gate_info,
 )
+from . import krylov  # noqa: F401
+from .krylov import (  # noqa: F401
+    KrylovResult,
+    krylov_combine_,
+    krylov_dots,
+    krylov_evolve,
+    krylov_info,
+    lanczos,
+    lanczos_ground_state,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

@@ -180,6 +180,24 @@ WGATE_MAX_K = 5
 WGATE_TILE_BITS = {ARTN_C64: 12, ARTN_C128: 11}
 WGATE_TABLE_HEADER_BYTES = 480
 
+KRYLOV_BATCH = 8
+KRYLOV_MAX_VECS = 64
+
+
+class ArtnKrylovInfo(ctypes.Structure):
+    _fields_ = [
+        ("grid", ctypes.c_int32),
+        ("batch", ctypes.c_int32),
+        ("dots_launches", ctypes.c_int32),
+        ("combine_launches", ctypes.c_int32),
+        ("dots_workspace_bytes", ctypes.c_int64),
+        ("combine_workspace_bytes", ctypes.c_int64),
+        ("dots_bytes_read", ctypes.c_int64),
+        ("combine_bytes_read", ctypes.c_int64),
+        ("combine_bytes_written", ctypes.c_int64),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -277,6 +295,12 @@ _EXPORTS = {
                                        ctypes.c_void_p, ctypes.c_int64]),
     "artn_wgate_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: the vector algebra of Krylov drivers (has("artn_krylov_combine"))
+    "artn_krylov_query": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ArtnKrylovInfo)]),
+    "artn_krylov_dots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_krylov_combine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 

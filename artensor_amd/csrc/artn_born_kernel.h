@@ -136,13 +136,17 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_overlap(const T
 }
 
 // out4 = {Re, Im, |a|^2, |b|^2}; nv = 1: the partials hold |a|^2 alone and out4 = {|a|^2, 0, |a|^2, |a|^2}
-static __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_finish(const double *__restrict__ partial, int n_partial, int nv,
-                                                                        double *__restrict__ out4) {
-  __shared__ double red[ARTN_BORN_THREADS][4];
+// (the sums of the finish, left in red[0][0..4): artn_krylov_kernel.h finishes its groups of four partials with the same code)
+__device__ __forceinline__ void born_finish_sum(const double *__restrict__ partial, int n_partial, int nv, double (*red)[4]) {
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int g = threadIdx.x; g < n_partial; g += ARTN_BORN_THREADS)
     for (int q = 0; q < nv; ++q) acc[q] += partial[(long)g * nv + q];
   born_wg_tree<4>(red, acc);
+}
+static __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_finish(const double *__restrict__ partial, int n_partial, int nv,
+                                                                        double *__restrict__ out4) {
+  __shared__ double red[ARTN_BORN_THREADS][4];
+  born_finish_sum(partial, n_partial, nv, red);
   if (threadIdx.x == 0) {
     if (nv == 1) {
       out4[0] = red[0][0], out4[1] = 0.0, out4[2] = red[0][0], out4[3] = red[0][0];

@@ -23,3 +23,4 @@
 #include "artn_pauli.hip" // (artn_pauli_kernel.h, artn_pauli_apply_kernel.h, artn_pauli_evolve_kernel.h)
 #include "artn_gates.hip" // (artn_gates_kernel.h)
 #include "artn_wgate.hip" // (artn_wgate_kernel.h)
+#include "artn_krylov.hip" // (artn_krylov_kernel.h)

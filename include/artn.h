@@ -668,6 +668,45 @@ int artn_wgate_pack(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, c
 int artn_wgate_apply(const ArtnMarginalDesc *d, void *a, int32_t k, const int32_t *dims, const void *table, int64_t table_bytes,
                      void *stream);
 
+/* ---- the vector algebra of Krylov drivers (additive to ABI 9: has("artn_krylov_combine")) ------------------------------------
+ * Vectors are complex64 or complex128 arrays of n elements (1 <= n <= 2^40) in DEVICE memory, 16-byte aligned; every vector of a
+ * call has the same dtype and the same dense layout, so the kernels work on the flat memory range.  float64 arithmetic in an
+ * order fixed by n alone, no atomics: results are bit-identical from run to run.
+ *
+ * artn_krylov_dots: out[2j], out[2j + 1] = Re, Im <V_j|w> for j < m and out[2m] = |w|^2 (DEVICE memory, 2m + 1 doubles), each bit
+ *   for bit what artn_born_overlap(V_j, w) reports as <a|b> and |b|^2, whatever m is.  The vectors are taken ARTN_KRYLOV_BATCH at a
+ *   time: ceil(m / ARTN_KRYLOV_BATCH) streaming launches, each reading w once and its V_j once, and one finish launch.
+ * artn_krylov_combine: y <- sum_{j < m} c_j X_j in ONE streaming launch, m <= ARTN_KRYLOV_MAX_VECS, c_j = coeff[2j] + i coeff[2j + 1]
+ *   (HOST memory; they travel in the kernel arguments), and out4 (DEVICE memory, 4 doubles, laid out as artn_born_overlap's with
+ *   b = NULL: {|y|^2, 0, |y|^2, |y|^2}) = the norm of the values as stored, bit for bit artn_born_overlap(y, NULL) of the result.
+ *   Every component is one float64 fma chain over j in the caller's order -- the real part takes c_r x_r then -c_i x_i, the imaginary
+ *   part c_r x_i then c_i x_r -- that starts from the first product and is rounded once, at the store.  A term whose coefficient is
+ *   exactly 0 + 0i is dropped before the launch (its vector is never read; all dropped: y = 0).  y may BE one of the X_j (the same
+ *   pointer); any other overlap of y with an X_j is refused.
+ * Both run on `stream` with a caller-supplied workspace and do no allocation, copy or synchronisation.
+ * ARTN_E_INVALID: a null pointer, m < 1, m above ARTN_KRYLOV_MAX_VECS (combine), n out of range, a workspace below the query's,
+ * a partial overlap, a coefficient that is not finite.  ARTN_E_UNSUPPORTED: another dtype, a pointer that is not 16-byte aligned.
+ * ARTN_E_NODEVICE without a device. */
+#define ARTN_KRYLOV_BATCH 8     /* vectors per launch of artn_krylov_dots (at most 16; DESIGN section 16 has the register table) */
+#define ARTN_KRYLOV_MAX_VECS 64 /* vectors of one artn_krylov_combine                                                          */
+typedef struct ArtnKrylovInfo {
+  int32_t grid;             /* workgroups of every streaming launch: artn_born_plan's overlap_grid                  */
+  int32_t batch;            /* ARTN_KRYLOV_BATCH                                                                     */
+  int32_t dots_launches;    /* streaming launches of artn_krylov_dots: ceil(m / batch); one finish launch follows   */
+  int32_t combine_launches; /* streaming launches of artn_krylov_combine: 1; one finish launch follows              */
+  int64_t dots_workspace_bytes;    /* 32 bytes x grid x (ceil(m / 2) + 1)                                            */
+  int64_t combine_workspace_bytes; /* 8 bytes x grid                                                                 */
+  int64_t dots_bytes_read;         /* nominal: (m + dots_launches) vectors                                           */
+  int64_t combine_bytes_read;      /* nominal: m vectors (terms with a zero coefficient included)                    */
+  int64_t combine_bytes_written;   /* one vector                                                                     */
+} ArtnKrylovInfo;
+/* Host-only: validates n, dtype and m (m >= 1; artn_krylov_combine itself refuses m above ARTN_KRYLOV_MAX_VECS). */
+int artn_krylov_query(int64_t n, int32_t dtype, int32_t m, ArtnKrylovInfo *info);
+int artn_krylov_dots(const void *const *vecs, int32_t m, const void *w, int64_t n, int32_t dtype, void *ws, int64_t ws_bytes,
+                     double *out, void *stream);
+int artn_krylov_combine(void *y, const double *coeff, const void *const *xs, int32_t m, int64_t n, int32_t dtype, void *ws,
+                        int64_t ws_bytes, double *out4, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
