@@ -163,7 +163,9 @@ def lanczos(op, v0, m, reorthogonalize="full", tol=None, keep_basis=True):
     when the first sweep left less than half of |w|; "none" removes v_j, and beta_{j-1} v_{j-1} from the recurrence.  alpha_j is
     the real part of <v_j|w>.  The run ends early, converged, at a breakdown (beta_j <= 2^-40 times the largest of the earlier
     betas and |op(v_0)|) and, with `tol`, once |beta_j s_j| of the lowest Ritz pair is below tol.  keep_basis=False (only with
-    "none") holds three vectors and returns Ritz values alone.  Returns a KrylovResult."""
+    "none") holds three vectors and returns Ritz values alone.  The threshold 2^-40 is fixed: with "none" and complex64 storage the
+    beta of an invariant subspace is rounding of complex64 (about 1e-6), so no breakdown is detected and the run goes on with Ritz
+    values off the spectrum; "full" detects it in both dtypes.  Returns a KrylovResult."""
     what = "krylov.lanczos"
     n = _checked(v0, what)
     m = int(m)
@@ -280,7 +282,8 @@ def lanczos_ground_state(amps0, terms, max_iter=200, tol=None, reorthogonalize="
     """(E0, state, info): the lowest Ritz value of H = sum_k c_k P_k (real c_k) from the start vector amps0, its normalised Ritz
     vector in the layout of amps0 (ONE krylov_combine_ over the basis) and a KrylovResult.  The run stops once the residual estimate
     is below tol (default: sqrt(eps of the dtype) * sum |c_k|) or after max_iter steps.  A basis holds at most 64 vectors: a run
-    that needs more restarts the recurrence from the current Ritz vector (a plain restart; info.restarts counts them)."""
+    that needs more restarts the recurrence from the current Ritz vector (a plain restart; info.restarts counts them).  info.alphas
+    is one array over all runs; info.betas is a LIST with one array per run (a restart has no beta that joins two runs)."""
     what = "krylov.lanczos_ground_state"
     _native.require_gpu(amps0, what)
     terms = _real_terms(terms, what)

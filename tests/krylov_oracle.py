@@ -51,22 +51,26 @@ def tridiagonal(alphas, betas):
 
 def lanczos_numpy(h, v0, m, reorthogonalize="full", tol=None, store=None):
     """The recurrence on a dense matrix `h` in complex128.  store=np.complex64 rounds every vector the device run stores in
-    that dtype (the normalised start, each op(v), each orthogonalised w, each scaled v).  Returns a dict: alphas [k], betas
-    [k - 1], beta_last, basis [n, k], converged, residual, iterations."""
+    that dtype (the normalised start, each op(v), each orthogonalised w, each scaled v).  `h` may be a callable v -> h v.  Returns a
+    dict: alphas [k], betas [k - 1], beta_last, basis [n, k], converged, breakdown, residual, iterations, norm0, and per step
+    first_sweep [k] = |w after the first sweep|^2 / |op(v)|^2 (a second sweep ran where it is below 0.25; "full" only), and
+    breakdown_ratio = beta / (2^-40 scale) of the last step taken (inf where scale is 0 and beta is not)."""
     rnd = (lambda x: x.astype(store).astype(np.complex128)) if store is not None else (lambda x: x)
     v0 = np.asarray(v0, dtype=np.complex128).reshape(-1)
     norm0 = math.sqrt(np.vdot(v0, v0).real)
     v = rnd(v0 * (1.0 / norm0))
     basis, alphas, betas = [v], [], []
-    beta_last, scale, residual, converged = 0.0, 0.0, None, False
+    beta_last, scale, residual, converged, breakdown, first_sweep, ratio = 0.0, 0.0, None, False, False, [], None
+    apply = h if callable(h) else (lambda x: h @ x)
     for j in range(m):
-        w = rnd(h @ v)
+        w = rnd(apply(v))
         nw = np.vdot(w, w).real
         if reorthogonalize == "full":
             vm = np.stack(basis, axis=1)
             hh = vm.conj().T @ w
             alpha = hh[j].real
             w = rnd(w - vm @ hh)
+            first_sweep.append(np.vdot(w, w).real / nw if nw else 0.0)
             if np.vdot(w, w).real < 0.25 * nw:
                 hh = vm.conj().T @ w
                 alpha += hh[j].real
@@ -81,8 +85,9 @@ def lanczos_numpy(h, v0, m, reorthogonalize="full", tol=None, store=None):
         beta = math.sqrt(np.vdot(w, w).real)
         if j == 0:
             scale = math.sqrt(nw)
+        ratio = beta / (BREAKDOWN * scale) if scale else (math.inf if beta else 0.0)
         if beta <= BREAKDOWN * scale:
-            converged, beta_last, residual = True, 0.0, 0.0
+            converged, breakdown, beta_last, residual = True, True, 0.0, 0.0
             break
         scale = max(scale, beta)
         beta_last = beta
@@ -98,7 +103,27 @@ def lanczos_numpy(h, v0, m, reorthogonalize="full", tol=None, store=None):
         v = rnd(w * (1.0 / beta))
         basis.append(v)
     return {"alphas": np.array(alphas), "betas": np.array(betas), "beta_last": beta_last, "basis": np.stack(basis, axis=1),
-            "converged": converged, "residual": residual, "iterations": len(alphas), "norm0": norm0}
+            "converged": converged, "breakdown": breakdown, "residual": residual, "iterations": len(alphas), "norm0": norm0,
+            "first_sweep": np.array(first_sweep), "breakdown_ratio": ratio}
+
+
+def ground_state_numpy(h, v0, max_iter, tol, reorthogonalize="full", store=None, max_vecs=64):
+    """lanczos_ground_state of artensor_amd/krylov.py on dense arrays: runs of at most max_vecs steps, each followed by the Ritz
+    vector basis[:, :k] @ s[:, 0] of its lowest Ritz pair, rounded to `store`; the next run starts from that vector unless the run
+    converged or max_iter steps are done.  Returns (E0, state, iterations, restarts, runs, last): runs the step count of every
+    run, last the dict of the last one."""
+    rnd = (lambda x: x.astype(store).astype(np.complex128)) if store is not None else (lambda x: x)
+    x, done, restarts, runs = np.asarray(v0, dtype=np.complex128).reshape(-1), 0, 0, []
+    while True:
+        r = lanczos_numpy(h, x, min(max_vecs, max_iter - done), reorthogonalize, tol=tol, store=store)
+        k = r["iterations"]
+        theta, s = np.linalg.eigh(tridiagonal(r["alphas"], r["betas"]))
+        state = rnd(r["basis"][:, :k] @ s[:, 0])
+        done += k
+        runs.append(k)
+        if r["converged"] or done >= max_iter:
+            return float(theta[0]), state, done, restarts, runs, r
+        x, restarts = state, restarts + 1
 
 
 def evolve_numpy(h, v0, t, m, store=None):

@@ -235,3 +235,40 @@ def test_the_numpy_restatement_of_the_recurrence_against_eigvalsh(store):
         v6 = v6.astype(store).astype(np.complex128)
     out, est = KO.evolve_numpy(h6, v6, 2.0 / c6, 64, store=store)
     assert np.linalg.norm(out - KO.expm_exact(h6, v6, 2.0 / c6)) <= 64 * 64 * 2.0 ** -p * 3.0 * np.linalg.norm(v6)
+
+
+RESTART_CASES = [(np.complex64, 70, [64, 6], False), (np.complex64, 130, [64, 64, 2], False), (None, 70, [64, 1], True)]
+
+
+@pytest.mark.parametrize("store,max_iter,runs,converged", RESTART_CASES, ids=["c64-70", "c64-130", "c128-70"])
+def test_the_restatement_of_the_restarted_ground_state_against_eigvalsh(store, max_iter, runs, converged):
+    """ground_state_numpy, the oracle of the restart tests of test_krylov_drivers_gpu.py, on their input: the 10-qubit Ising
+    chain at h = 1.5 with tol = 0, so that only a breakdown ends a run early.  With complex64 storage 70 steps are runs of 64 and
+    6 and 130 steps runs of 64, 64 and 2; in complex128 the restart vector is an eigenvector to rounding and the second run breaks
+    down at its first step.  The margin of that breakdown is printed: beta / (2^-40 scale) of the last step, measured 2.5e-3."""
+    p = 53 if store is None else 24
+    terms = KO.ising_terms(10, 1.0, 1.5)
+    h = KO.dense_hamiltonian(terms, 10)
+    lam = np.linalg.eigvalsh(h)
+    c = sum(abs(x) for x, _ in terms)
+    rng = np.random.default_rng(10)                               # start_vector(10, dtype, 10) of the GPU tests
+    v0 = (rng.standard_normal(1024) + 1j * rng.standard_normal(1024)).astype(np.complex128 if store is None else store)
+    e0, state, done, restarts, got_runs, last = KO.ground_state_numpy(h, v0, max_iter, 0.0, "full", store=store)
+    x = state / np.linalg.norm(state)
+    res = np.linalg.norm(h @ x - e0 * x)
+    print(f"{'complex128' if store is None else 'complex64'} max_iter {max_iter}: runs {got_runs}, E0 - lambda_0 {e0 - lam[0]:.3e}, |r| {res:.3e}, "
+          f"last beta / (2^-40 scale) {last['breakdown_ratio']:.3e}")
+    assert got_runs == runs and done == sum(runs) and restarts == len(runs) - 1
+    assert last["converged"] == converged == last["breakdown"] and last["iterations"] == runs[-1]
+    assert res <= 64 * max_iter * 2.0 ** -p * c and abs(e0 - lam[0]) <= 64 * max_iter * 2.0 ** -p * c
+    assert abs(e0 - lam[0]) < abs(e0 - lam[1])
+    if store is not None:                                         # (in complex128 both sides are rounding of eigvalsh and of h @ x)
+        assert abs(e0 - lam[0]) <= res
+    if converged:
+        assert last["breakdown_ratio"] <= 1.0 and last["residual"] == 0.0 == last["beta_last"]
+    # one run is lanczos_numpy itself, and max_vecs cuts the runs
+    one = KO.lanczos_numpy(h, v0, 40, "full", tol=0.0, store=store)
+    e1, _, done1, restarts1, runs1, last1 = KO.ground_state_numpy(h, v0, 40, 0.0, "full", store=store)
+    assert runs1 == [40] and restarts1 == 0 and done1 == 40 and np.array_equal(one["alphas"], last1["alphas"])
+    assert e1 == np.linalg.eigh(KO.tridiagonal(one["alphas"], one["betas"]))[0][0]
+    assert KO.ground_state_numpy(h, v0, 40, 0.0, "full", store=store, max_vecs=16)[4] == [16, 16, 8]

@@ -57,14 +57,14 @@ def case_id(c):
 @pytest.mark.parametrize("case", layout_cases(), ids=case_id)
 def test_dots_against_numpy_and_bit_for_bit_against_overlap(case, dtype):
     shape, perm = case
-    vs, hs = vectors(2 * B + 2, shape, dtype, 11, perm)
+    vs, hs = vectors(65, shape, dtype, 11, perm)                # a full basis: m = 64 is 64 / B launches into one workspace
     w, hw = vs[-1], hs[-1]
     vs, hs = vs[:-1], hs[:-1]
     n = hw.size
     ref = [A.overlap(v, w) for v in vs]                        # (<v|w>, |v|^2, |w|^2): the exact reference, computed once
     want = [np.vdot(h, hw) for h in hs]
     bound = [4 * (n + 4) * 2.0 ** -53 * float(np.sum(np.abs(h) * np.abs(hw))) for h in hs]
-    for m in (1, 2, B, B + 1, 2 * B + 1):
+    for m in (1, 2, B, B + 1, 2 * B + 1, 63, 64):
         dots, nw = A.krylov_dots(vs[:m], w)
         assert dots.shape == (m,) and dots.dtype == np.complex128
         for j in range(m):
