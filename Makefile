@@ -19,6 +19,7 @@ MAIN_HDRS := $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/ar
 BORN_SRCS := $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
 RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(HOST_HDRS)
 PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pauli_apply_kernel.h $(CSRC)/artn_pauli_evolve_kernel.h \
+              $(CSRC)/artn_pauli_adjoint_kernel.h \
               $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
 GATES_SRCS := $(CSRC)/artn_gates.hip $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
 WGATE_SRCS := $(CSRC)/artn_wgate.hip $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)

@@ -78,6 +78,13 @@ from .pauli import (  # noqa: F401
     pauli_sum_variance,
     trotter_steps,
 )
+from . import adjoint  # noqa: F401
+from .adjoint import (  # noqa: F401
+    PauliPairCircuit,
+    adjoint_gradient,
+    pauli_adjoint_info,
+    pauli_evolve_pair_,
+)
 from . import gates  # noqa: F401
 from .gates import (  # noqa: F401
     GateCircuit,

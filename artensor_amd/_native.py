@@ -145,6 +145,22 @@ class ArtnPauliEvolveInfo(ctypes.Structure):
 PAULI_EVOLVE_MAX_RANK = 4
 
 
+class ArtnPauliAdjointInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_runs", ctypes.c_int32),
+        ("n_launches", ctypes.c_int32),
+        ("max_rank", ctypes.c_int32),
+        ("n_measured", ctypes.c_int32),
+        ("table_bytes", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
+PAULI_ADJOINT_MAX_RANK = 3
+
+
 class ArtnGatesInfo(ctypes.Structure):
     _fields_ = [
         ("n_runs", ctypes.c_int32),
@@ -279,6 +295,16 @@ _EXPORTS = {
                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
     "artn_pauli_evolve": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: the same circuits on two states with transition elements (has("artn_pauli_adjoint"))
+    "artn_pauli_adjoint_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ArtnPauliAdjointInfo), ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_pauli_adjoint_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
+    "artn_pauli_adjoint": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     # additive to ABI 9 as well: in-place circuits of dense one- and two-qubit gates (has("artn_gates_apply"))
     "artn_gates_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ArtnGatesInfo), ctypes.c_void_p,

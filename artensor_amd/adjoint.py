@@ -1,0 +1,172 @@
+"""Adjoint gradients of circuits of Pauli rotations (C ABI: artn_pauli_adjoint_query, artn_pauli_adjoint_pack,
+artn_pauli_adjoint): the in-place circuits of pauli.py applied to TWO states at once, with the transition element
+t_k = <lam| P_k |phi> of every measured step taken immediately before the step.
+
+With U = U_K ... U_1, U_k = exp(-i theta_k P_k), phi_k = U_k ... U_1 psi0 and lam_k = (U_K ... U_{k+1})^+ H phi_K,
+
+    dE/dtheta_k = 2 Im <lam_k| P_k |phi_k>      for E = <psi0| U^+ H U |psi0>,
+
+so one forward circuit, one H|phi> and one backward sweep of the reversed circuit with negated angles give all K derivatives.
+
+After a call both tensors are bit for bit what pauli_evolve_ leaves on each alone, for every max_rank and every measure pattern.
+The transition elements are sums in float64 in a fixed order: bit-identical from run to run for one plan; the order follows the
+blocks of the runs, so they may differ in the last bits between max_rank values.  There is no CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _native
+from .born import _DTYPES, _checked, norm2, overlap
+from .pauli import PauliCircuit, PauliSumOperator, _desc, _max_rank, _ptr, _split_steps
+
+__all__ = ["pauli_adjoint_info", "PauliPairCircuit", "pauli_evolve_pair_", "adjoint_gradient"]
+
+
+def _flags(measure, n_steps):
+    """uint8 [n_steps] (None: every step)."""
+    if measure is None:
+        return np.ones(n_steps, dtype=np.uint8)
+    flags = np.ascontiguousarray([1 if bool(f) else 0 for f in measure], dtype=np.uint8)
+    if flags.shape != (n_steps,):
+        raise ValueError(f"measure: one flag per step expected ({n_steps}), got {len(flags)}")
+    return flags
+
+
+def _adjoint_query(d, ops, coeff, flags, max_rank, arrays=False):
+    n = ops.shape[0]
+    info = _native.ArtnPauliAdjointInfo()
+    if arrays:
+        xm, zm = (np.zeros(n, dtype=np.uint64) for _ in range(2))
+        ny, run, slot, rank = (np.zeros(n, dtype=np.int32) for _ in range(4))
+        basis = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.uint64)
+        pivot = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.int32)
+        out = (xm, zm, ny, run, slot, rank, basis, pivot)
+        ptrs = [_ptr(x) for x in out]
+    else:
+        out, ptrs = (), [None] * 8
+    _native.check(_native.lib().artn_pauli_adjoint_query(ctypes.byref(d), _ptr(ops), _ptr(coeff), _ptr(flags), n, max_rank,
+                                                         ctypes.byref(info), *ptrs))
+    return (info,) + out
+
+
+def pauli_adjoint_info(shape, strides, steps, dtype=torch.complex64, measure=None, max_rank=None):
+    """Host-only: how a two-state circuit is cut into runs (the cuts of pauli_evolve_info at the same effective max_rank; the
+    default and the maximum lie one below the single-state ones).  The per-step and per-run lists of pauli_evolve_info, `measure`,
+    n_measured, n_runs, n_launches = n_runs + 1 (the finish), table_bytes, workspace_bytes and bytes_read = bytes_written =
+    2 * n_runs * bytes of a state."""
+    if dtype not in _DTYPES:
+        raise TypeError(f"pauli_adjoint_info: complex64 or complex128 expected, got {dtype}")
+    coeff, ops = _split_steps(steps, len(shape))
+    flags = _flags(measure, ops.shape[0])
+    info, xm, zm, ny, run, slot, rank, basis, pivot = _adjoint_query(_desc(shape, strides, dtype), ops, coeff, flags,
+                                                                     _max_rank(max_rank), arrays=True)
+    nr = info.n_runs
+    ranks = [int(v) for v in rank[:nr]]
+    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny],
+            "alpha": [complex(c[0], c[1]) for c in coeff], "beta": [complex(c[2], c[3]) for c in coeff],
+            "run": [int(v) for v in run], "slot_mask": [int(v) for v in slot], "measure": [bool(f) for f in flags],
+            "n_measured": info.n_measured, "n_runs": nr, "n_launches": info.n_launches, "max_rank": info.max_rank, "run_rank": ranks,
+            "run_basis": [[int(v) for v in basis[r, :ranks[r]]] for r in range(nr)],
+            "run_pivot": [[int(v) for v in pivot[r, :ranks[r]]] for r in range(nr)],
+            "table_bytes": info.table_bytes, "workspace_bytes": info.workspace_bytes, "bytes_read": info.bytes_read,
+            "bytes_written": info.bytes_written}
+
+
+class PauliPairCircuit:
+    """The steps of a PauliCircuit for TWO tensors of one layout: validates, cuts the runs, packs the table and copies it to
+    `device` once; the workspace is allocated per call, so an instance holds no state that two calls share.  circ(lam, phi,
+    device=False) updates both IN PLACE (one launch per run and a finish launch) and returns t[k] = <lam| P_k |phi> taken
+    immediately before step k, 0 for the steps `measure` leaves out: complex128 numpy [K], or with device=True a float64 GPU
+    tensor [K, 2] without a host synchronisation."""
+
+    def __init__(self, shape, strides, dtype, steps, device, measure=None, max_rank=None):
+        if dtype not in _DTYPES:
+            raise TypeError(f"PauliPairCircuit: complex64 or complex128 expected, got {dtype}")
+        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"PauliPairCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU "
+                               "fallback")
+        coeff, self._ops = _split_steps(steps, len(self.shape))
+        flags = _flags(measure, self._ops.shape[0])
+        self._d = _desc(self.shape, self.strides, dtype)
+        self._max_rank = _max_rank(max_rank)
+        info = _adjoint_query(self._d, self._ops, coeff, flags, self._max_rank)[0]
+        table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
+        _native.check(_native.lib().artn_pauli_adjoint_pack(ctypes.byref(self._d), _ptr(self._ops), _ptr(coeff), _ptr(flags),
+                                                            self._ops.shape[0], self._max_rank, _ptr(table), info.table_bytes))
+        self.n_steps, self.n_runs, self.max_rank = self._ops.shape[0], info.n_runs, info.max_rank
+        self.table_bytes, self.workspace_bytes = info.table_bytes, info.workspace_bytes
+        self._table = torch.from_numpy(table.view(np.uint8)).to(self.device)
+
+    def __call__(self, lam, phi, device=False):
+        what = "adjoint.PauliPairCircuit"
+        for x in (lam, phi):
+            _checked(x, what)
+            if tuple(x.shape) != self.shape or tuple(x.stride()) != self.strides or x.dtype != self.dtype:
+                raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
+                                 f"{tuple(x.shape)}, {tuple(x.stride())}, {x.dtype}")
+            if x.device != self._table.device:
+                raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {x.device}")
+        nbytes = phi.numel() * phi.element_size()
+        if lam.data_ptr() < phi.data_ptr() + nbytes and phi.data_ptr() < lam.data_ptr() + nbytes:
+            raise ValueError(f"{what}: lam overlaps phi")
+        out = torch.empty((self.n_steps, 2), dtype=torch.float64, device=phi.device)
+        ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)   # (per call: calls may overlap on streams)
+        with torch.cuda.device(phi.device):
+            _native.check(_native.lib().artn_pauli_adjoint(ctypes.byref(self._d), lam.data_ptr(), phi.data_ptr(), _ptr(self._ops),
+                                                           self.n_steps, self._max_rank, self._table.data_ptr(), self.table_bytes,
+                                                           ws.data_ptr(), self.workspace_bytes, out.data_ptr(),
+                                                           _native.current_stream_ptr(phi.device)))
+        return out if device else out.cpu().numpy().view(np.complex128).reshape(self.n_steps)
+
+
+def pauli_evolve_pair_(lam, phi, steps, measure=None, max_rank=None, device=False):
+    """The circuit `steps` (see pauli.PauliCircuit) applied to lam and to phi in place, and the transition elements of the
+    measured steps (see PauliPairCircuit)."""
+    _checked(phi, "adjoint.pauli_evolve_pair_")
+    return PauliPairCircuit(phi.shape, phi.stride(), phi.dtype, steps, phi.device, measure, max_rank)(lam, phi, device)
+
+
+def adjoint_gradient(amps0, rotations, terms, params=None, normalize=True, max_rank=None):
+    """(E, grad) of E = <amps0| U^+ H U |amps0>, U = the rotations [(theta, string), ...] applied in list order, H = sum_k c_k P_k
+    with REAL c_k (terms = [(c_k, string_k), ...]), by the adjoint method: a forward PauliCircuit, one PauliSumOperator, one overlap
+    and one PauliPairCircuit of the reversed rotations with negated angles.  params: None (one parameter per rotation) or one
+    integer per rotation: -1 marks a constant rotation (not measured, no entry), equal indices share a parameter and their
+    derivatives are added in float64 in rotation order; grad is float64 numpy of length K or max(params) + 1.  normalize=True
+    divides E and grad by sum |amps0|^2.  max_rank: the two-state limits (3 / 2) apply to both circuits.  amps0 is never written; the peak extra memory is two state-sized tensors."""
+    _native.require_gpu(amps0, "adjoint.adjoint_gradient")
+    _checked(amps0, "adjoint.adjoint_gradient")
+    rotations, terms = list(rotations), list(terms)
+    if any(complex(c).imag != 0.0 for c, _ in terms):
+        raise ValueError("adjoint_gradient takes real coefficients (a Hermitian sum)")
+    if any(not isinstance(r, (tuple, list)) or len(r) != 2 for r in rotations):
+        raise ValueError("adjoint_gradient: rotations are (theta, string) pairs")
+    n_rot = len(rotations)
+    if params is None:
+        params = list(range(n_rot))
+    else:
+        params = [int(p) for p in params]
+        if len(params) != n_rot or any(p < -1 for p in params):
+            raise ValueError(f"params: one integer >= -1 per rotation expected ({n_rot})")
+    shape, strides, dtype, dev = amps0.shape, amps0.stride(), amps0.dtype, amps0.device
+    back = [(-float(theta), string) for theta, string in reversed(rotations)]
+    # built first: max_rank follows the two-state limits, and a refusal comes before any work on the device
+    sweep = PauliPairCircuit(shape, strides, dtype, back, dev, [p >= 0 for p in reversed(params)], max_rank)
+    phi = torch.empty_strided(shape, strides, dtype=dtype, device=dev)
+    phi.copy_(amps0)
+    PauliCircuit(shape, strides, dtype, rotations, dev, max_rank)(phi)
+    lam = PauliSumOperator(shape, strides, dtype, terms, dev)(phi)
+    energy = overlap(phi, lam)[0].real
+    t = sweep(lam, phi)
+    # the sweep runs with the negated angles: U_k^+ = exp(+i theta_k P_k), and t is taken before U_k^+ is applied
+    grad = np.zeros(max(params) + 1 if params else 0, dtype=np.float64)
+    for k, p in enumerate(params):
+        if p >= 0:
+            grad[p] += 2.0 * t[n_rot - 1 - k].imag
+    if normalize:
+        n2 = norm2(amps0)
+        energy, grad = energy / n2, grad / n2
+    return energy, grad

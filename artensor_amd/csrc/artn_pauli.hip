@@ -1,5 +1,6 @@
 // artn_pauli.hip -- host half of the Pauli-string entry points of include/artn.h (kernels: artn_pauli_kernel.h for the
-// expectation values, artn_pauli_apply_kernel.h for y = H a, artn_pauli_evolve_kernel.h for the in-place circuits).
+// expectation values, artn_pauli_apply_kernel.h for y = H a, artn_pauli_evolve_kernel.h for the in-place circuits,
+// artn_pauli_adjoint_kernel.h for the same circuits on two states with transition elements).
 //
 // A translation unit of its own (build/obj/pauli.o).
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 #include "artn_pauli_kernel.h"
 #include "artn_pauli_apply_kernel.h"
 #include "artn_pauli_evolve_kernel.h"
+#include "artn_pauli_adjoint_kernel.h"
 
 struct PauliPlan {
   int64_t n = 1;
@@ -409,17 +411,10 @@ static hipError_t pauli_evolve_launch(const PauliEvolvePlan &ep, T *a, const voi
   return hipSuccess;
 }
 
-extern "C" {
-
-int artn_pauli_evolve_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
-                            ArtnPauliEvolveInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run,
-                            int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot) {
-  if (!info) return fail(ARTN_E_INVALID, "null info");
-  if (!coeff) return fail(ARTN_E_INVALID, "null pointer");
-  PauliEvolvePlan ep;
-  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
+// the per-step and per-run arrays of a query (any may be NULL)
+static void pauli_evolve_report(const PauliEvolvePlan &ep, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run, int32_t *slot_mask,
+                                int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot) {
   const PauliPlan &pl = ep.pl;
-  *info = ep.info;
   if (xmask) std::copy(pl.xm.begin(), pl.xm.end(), xmask);
   if (zmask) std::copy(pl.zm.begin(), pl.zm.end(), zmask);
   if (n_y) std::copy(pl.ny.begin(), pl.ny.end(), n_y);
@@ -433,17 +428,12 @@ int artn_pauli_evolve_query(const ArtnMarginalDesc *d, const uint8_t *ops, const
       if (run_pivot) run_pivot[r * ARTN_PAULI_EVOLVE_MAX_RANK + j] = j < rp.pivot.size() ? rp.pivot[j] : -1;
     }
   }
-  return ARTN_OK;
 }
 
-int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
-                           void *table, int64_t table_bytes) {
-  PauliEvolvePlan ep;
-  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
-  if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ep.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_evolve_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve_pack needs an 8-byte aligned table");
+// the table of include/artn.h into host memory (at least ep.info.table_bytes)
+static void pauli_evolve_fill(const PauliEvolvePlan &ep, const double *coeff, void *table) {
   const PauliPlan &pl = ep.pl;
+  const int64_t n_steps = (int64_t)pl.xm.size();
   const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
   ArtnPauliEvolveHeader *h = (ArtnPauliEvolveHeader *)table;
   ArtnPauliEvolveRun *runs = (ArtnPauliEvolveRun *)(h + 1);
@@ -461,6 +451,30 @@ int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const 
     stp[k] = ArtnPauliEvolveStep{pl.xm[k] & in, (uint64_t)ep.slot_mask[k], pl.zm[k], (uint64_t)pl.ny[k],
                                  coeff[4 * k], coeff[4 * k + 1], coeff[4 * k + 2], coeff[4 * k + 3]};
   }
+}
+
+extern "C" {
+
+int artn_pauli_evolve_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
+                            ArtnPauliEvolveInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run,
+                            int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot) {
+  if (!info) return fail(ARTN_E_INVALID, "null info");
+  if (!coeff) return fail(ARTN_E_INVALID, "null pointer");
+  PauliEvolvePlan ep;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
+  *info = ep.info;
+  pauli_evolve_report(ep, xmask, zmask, n_y, run, slot_mask, run_rank, run_basis, run_pivot);
+  return ARTN_OK;
+}
+
+int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_steps, int32_t max_rank,
+                           void *table, int64_t table_bytes) {
+  PauliEvolvePlan ep;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
+  if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ep.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_evolve_query reports");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve_pack needs an 8-byte aligned table");
+  pauli_evolve_fill(ep, coeff, table);
   return ARTN_OK;
 }
 
@@ -476,6 +490,124 @@ int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, in
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) HIP_TRY(pauli_evolve_launch(ep, (float2 *)a, table, st));
   else HIP_TRY(pauli_evolve_launch(ep, (double2 *)a, table, st));
+  HIP_TRY(hipGetLastError());
+  return ARTN_OK;
+}
+
+} // extern "C"
+
+// The same circuits on two states with transition elements (include/artn.h: ADJOINT; kernels: artn_pauli_adjoint_kernel.h).
+// The plan is pauli_evolve_plan at the two-state rank; only the limits, the byte counts and the workspace are the adjoint's own.
+static int pauli_adjoint_plan(const ArtnMarginalDesc *d, const uint8_t *ops, const uint8_t *measure, int64_t n_steps, int32_t max_rank,
+                              PauliEvolvePlan &ep, ArtnPauliAdjointInfo &info) {
+  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
+  const int lib_max = d->dtype == ARTN_C128 ? ARTN_PAULI_ADJOINT_MAX_RANK - 1 : ARTN_PAULI_ADJOINT_MAX_RANK;
+  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
+  if (max_rank > lib_max && (d->dtype == ARTN_C64 || d->dtype == ARTN_C128))
+    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the two-state maximum " + std::to_string(lib_max) + " of this dtype");
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, std::min<int32_t>(max_rank < 0 ? lib_max - 1 : max_rank, lib_max), ep)) return rc;
+  int64_t flagged = n_steps;
+  if (measure) flagged = std::count_if(measure, measure + n_steps, [](uint8_t f) { return f != 0; });
+  const int64_t groups = std::min<int64_t>(std::max<int64_t>(ep.pl.n >> ARTN_PAULI_TILE_BITS, 1), ARTN_PAULI_EVOLVE_MAX_GRID);
+  info = ArtnPauliAdjointInfo{};
+  info.n_runs = ep.info.n_runs;
+  info.n_launches = ep.info.n_runs + 1;
+  info.max_rank = ep.info.max_rank;
+  info.n_measured = (int32_t)flagged;
+  info.table_bytes = ep.info.table_bytes;
+  info.workspace_bytes = n_steps * groups * ARTN_PAULI_ADJOINT_WAVES * 2 * (int64_t)sizeof(double);
+  info.bytes_read = 2 * ep.info.bytes_read;
+  info.bytes_written = 2 * ep.info.bytes_written;
+  return ARTN_OK;
+}
+
+template <typename T, int R>
+static hipError_t pauli_adjoint_launch_rank(T *lam, T *phi, long tiles, const ArtnPauliEvolveRun *run, const ArtnPauliEvolveStep *stp,
+                                            double *ws, long groups, hipStream_t st) {
+  const size_t lds = ((size_t)2 * sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
+  if (hipError_t e = ensure_lds<artn_k_pauli_adjoint<T, R>>(lds); e != hipSuccess) return e;
+  const long n_blocks = tiles >> R;
+  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_PAULI_EVOLVE_MAX_GRID));
+  hipLaunchKernelGGL((artn_k_pauli_adjoint<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, lam, phi, n_blocks, run, stp, ws, groups);
+  return hipSuccess;
+}
+
+template <typename T>
+static hipError_t pauli_adjoint_launch(const PauliEvolvePlan &ep, T *lam, T *phi, const void *table, double *ws, double *out, hipStream_t st) {
+  const ArtnPauliEvolveRun *runs = (const ArtnPauliEvolveRun *)((const ArtnPauliEvolveHeader *)table + 1);
+  const ArtnPauliEvolveStep *stp = (const ArtnPauliEvolveStep *)(runs + ep.runs.size());
+  const int64_t n = ep.pl.n;
+  const int n_steps = (int)ep.pl.xm.size();
+  const long tiles = (long)std::max<int64_t>(n >> ARTN_PAULI_TILE_BITS, 1);
+  const long groups = std::min<long>(tiles, ARTN_PAULI_EVOLVE_MAX_GRID);
+  if (n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
+    hipLaunchKernelGGL(artn_k_pauli_adjoint_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, lam, phi, (long)n, stp, n_steps, ws);
+  } else {
+    for (size_t r = 0; r < ep.runs.size(); ++r) {
+      hipError_t e = hipErrorInvalidValue;
+      switch ((int)ep.runs[r].basis.size()) {
+      case 0: e = pauli_adjoint_launch_rank<T, 0>(lam, phi, tiles, runs + r, stp, ws, groups, st); break;
+      case 1: e = pauli_adjoint_launch_rank<T, 1>(lam, phi, tiles, runs + r, stp, ws, groups, st); break;
+      case 2: e = pauli_adjoint_launch_rank<T, 2>(lam, phi, tiles, runs + r, stp, ws, groups, st); break;
+      case 3:
+        if constexpr (sizeof(T) == 8) e = pauli_adjoint_launch_rank<T, 3>(lam, phi, tiles, runs + r, stp, ws, groups, st);
+        break;
+      }
+      if (e != hipSuccess) return e;
+    }
+  }
+  hipLaunchKernelGGL(artn_k_pauli_adjoint_finish, dim3((unsigned)n_steps), dim3(ARTN_BORN_THREADS), 0, st, (const double *)ws, groups, tiles,
+                     stp, out);
+  return hipSuccess;
+}
+
+extern "C" {
+
+int artn_pauli_adjoint_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, const uint8_t *measure, int64_t n_steps,
+                             int32_t max_rank, ArtnPauliAdjointInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run,
+                             int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot) {
+  if (!info) return fail(ARTN_E_INVALID, "null info");
+  if (!coeff) return fail(ARTN_E_INVALID, "null pointer");
+  PauliEvolvePlan ep;
+  if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ep, *info)) return rc;
+  pauli_evolve_report(ep, xmask, zmask, n_y, run, slot_mask, run_rank, run_basis, run_pivot);
+  return ARTN_OK;
+}
+
+int artn_pauli_adjoint_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, const uint8_t *measure, int64_t n_steps,
+                            int32_t max_rank, void *table, int64_t table_bytes) {
+  PauliEvolvePlan ep;
+  ArtnPauliAdjointInfo info;
+  if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ep, info)) return rc;
+  if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_adjoint_query reports");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint_pack needs an 8-byte aligned table");
+  pauli_evolve_fill(ep, coeff, table);
+  ArtnPauliEvolveStep *stp = (ArtnPauliEvolveStep *)((ArtnPauliEvolveRun *)((ArtnPauliEvolveHeader *)table + 1) + ep.runs.size());
+  for (int64_t k = 0; k < n_steps; ++k) { // n_y, the measure flag and the rank of the step's run share a word
+    const uint64_t flag = !measure || measure[k] ? 1 : 0, rank = (uint64_t)ep.runs[ep.run_of[k]].basis.size();
+    stp[k].n_y |= flag << 8 | rank << 16;
+  }
+  return ARTN_OK;
+}
+
+int artn_pauli_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const uint8_t *ops, int64_t n_steps, int32_t max_rank,
+                       const void *table, int64_t table_bytes, void *workspace, int64_t workspace_bytes, double *out, void *stream) {
+  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
+  PauliEvolvePlan ep;
+  ArtnPauliAdjointInfo info;
+  if (int rc = pauli_adjoint_plan(d, ops, nullptr, n_steps, max_rank, ep, info)) return rc; // (coefficients and flags are in the table)
+  if (!lam || !phi || !table || !workspace || !out) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_adjoint_query reports");
+  if (workspace_bytes < info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_pauli_adjoint_query reports");
+  if ((((uintptr_t)lam | (uintptr_t)phi | (uintptr_t)workspace) & 15) != 0)
+    return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint needs 16-byte aligned arrays and workspace");
+  if ((((uintptr_t)table | (uintptr_t)out) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint needs an 8-byte aligned table and output");
+  const uintptr_t bytes = (uintptr_t)ep.pl.n * (d->dtype == ARTN_C64 ? 8 : 16), pl = (uintptr_t)lam, pp = (uintptr_t)phi;
+  if (pl < pp + bytes && pp < pl + bytes) return fail(ARTN_E_INVALID, "artn_pauli_adjoint: lam overlaps phi");
+  hipStream_t st = (hipStream_t)stream;
+  if (d->dtype == ARTN_C64) HIP_TRY(pauli_adjoint_launch(ep, (float2 *)lam, (float2 *)phi, table, (double *)workspace, out, st));
+  else HIP_TRY(pauli_adjoint_launch(ep, (double2 *)lam, (double2 *)phi, table, (double *)workspace, out, st));
   HIP_TRY(hipGetLastError());
   return ARTN_OK;
 }

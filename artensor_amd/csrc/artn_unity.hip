@@ -20,7 +20,7 @@
 #endif
 #include "artn_born.hip"
 #include "artn_rdm.hip"
-#include "artn_pauli.hip" // (artn_pauli_kernel.h, artn_pauli_apply_kernel.h, artn_pauli_evolve_kernel.h)
+#include "artn_pauli.hip" // (artn_pauli_kernel.h, artn_pauli_apply_kernel.h, artn_pauli_evolve_kernel.h, artn_pauli_adjoint_kernel.h)
 #include "artn_gates.hip" // (artn_gates_kernel.h)
 #include "artn_wgate.hip" // (artn_wgate_kernel.h)
 #include "artn_krylov.hip" // (artn_krylov_kernel.h)

@@ -508,6 +508,55 @@ int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, in
                       int64_t table_bytes, void *stream);
 
 /*
+ * ADJOINT: the same circuits on TWO arrays with transition elements (additive to ABI 9: look the symbols up before calling).
+ * `lam` and `phi` share one descriptor (shape, strides, dtype).  For every step k of the circuit, in order:
+ *     1. when the step is flagged in `measure` (uint8 [n_steps], non-zero = flagged; NULL flags every step),
+ *            t_k = sum_i conj(lam[i]) * b_i,   b_i = s (-i)^n_y phi[i ^ xmask] = (P_k phi)[i]   (ARITHMETIC above),
+ *        on the two arrays as they are immediately before step k: operands converted to float64, products accumulated by fma,
+ *        partial sums added in a fixed order -- no atomics, bit-identical from run to run for one plan.  The order follows the
+ *        blocks of the run, so t_k may differ in the last bits between max_rank values.  out[k] = Re t_k, Im t_k; 0, 0 for a
+ *        step that is not flagged;
+ *     2. step k is applied to phi and to lam with the ARITHMETIC above: each array ends bit for bit as artn_pauli_evolve leaves it
+ *        alone, for every max_rank and every measure.
+ * With lam = (U_K .. U_{k+1})^+ H phi_K and the reversed circuit of U_k^+, dE/dtheta_k = 2 Im t_k for U_k = exp(-i theta_k P_k).
+ *
+ * PLAN, runs, blocks and slots are those of artn_pauli_evolve at the same effective max_rank; a workgroup holds the 2^r tiles of a
+ * block of both arrays, so the ranks lie one lower: -1 selects 2 for complex64 and 1 for complex128 (64 KiB of LDS), the maximum is
+ * ARTN_PAULI_ADJOINT_MAX_RANK for complex64 and one less for complex128 (128 KiB); more is ARTN_E_UNSUPPORTED, below -1
+ * ARTN_E_INVALID.  One launch per run, then one finish launch.
+ *
+ * TABLE: the layout of artn_pauli_evolve_pack, same table_bytes; the n_y word of a step record also carries the flags:
+ *     bits 0..7   n_y        bit 8   1 when the step is measured        bits 16..23   the rank of the step's run
+ * WORKSPACE (device, 16-byte aligned): float64 [n_steps][G][4][2], G = min(max(n >> 10, 1), 2048) -- per step, workgroup and wave
+ * the Re and Im of a partial sum, written by plain stores; workspace_bytes = 64 * G * n_steps.  Needs no initialisation.
+ */
+#define ARTN_PAULI_ADJOINT_MAX_RANK 3
+typedef struct ArtnPauliAdjointInfo {
+  int32_t n_runs;          /* = the launches before the finish launch                */
+  int32_t n_launches;      /* n_runs + 1                                             */
+  int32_t max_rank;        /* the effective one, as ArtnPauliEvolveInfo              */
+  int32_t n_measured;      /* flagged steps                                          */
+  int64_t table_bytes;
+  int64_t workspace_bytes;
+  int64_t bytes_read;      /* 2 * n_runs * n * element size                          */
+  int64_t bytes_written;   /* the same                                               */
+} ArtnPauliAdjointInfo;
+/* Host-only: as artn_pauli_evolve_query (the same per-step and per-run arrays, run_basis and run_pivot [.][4]) at the two-state
+ * ranks. */
+int artn_pauli_adjoint_query(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, const uint8_t *measure, int64_t n_steps,
+                             int32_t max_rank, ArtnPauliAdjointInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run,
+                             int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query with the same max_rank). */
+int artn_pauli_adjoint_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, const uint8_t *measure, int64_t n_steps,
+                            int32_t max_rank, void *table, int64_t table_bytes);
+/* The circuit on `lam` and `phi`, in place, and out[n_steps][2] (device, 8-byte aligned), on `stream`.  `table` is DEVICE memory
+ * holding what artn_pauli_adjoint_pack wrote for the same descriptor, ops, n_steps and max_rank (8-byte aligned).  ARTN_E_INVALID: a
+ * null pointer, table_bytes or workspace_bytes below the query's, byte ranges of lam and phi that overlap; ARTN_E_UNSUPPORTED: lam,
+ * phi or workspace not 16-byte aligned.  No allocation, copy or synchronisation.  ARTN_E_NODEVICE without a device. */
+int artn_pauli_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const uint8_t *ops, int64_t n_steps, int32_t max_rank,
+                       const void *table, int64_t table_bytes, void *workspace, int64_t workspace_bytes, double *out, void *stream);
+
+/*
  * In-place circuits of dense one- and two-qubit gates (additive to ABI 9: look the symbols up before calling).  A CIRCUIT is an
  * ordered list of n_gates GATES; gate g acts on k[g] (1 or 2) distinct dimensions of extent 2, dims[g][0 .. k-1] (dims is int32
  * [n_gates][2]; the second entry of a one-qubit gate is ignored), with the matrix mat[g] (float64 [n_gates][32]: the 2^k x 2^k
