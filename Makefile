@@ -21,7 +21,7 @@ RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(HOST_HDRS)
 PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pauli_apply_kernel.h $(CSRC)/artn_pauli_evolve_kernel.h \
               $(CSRC)/artn_pauli_adjoint_kernel.h \
               $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
-GATES_SRCS := $(CSRC)/artn_gates.hip $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
+GATES_SRCS := $(CSRC)/artn_gates.hip $(CSRC)/artn_gates_kernel.h $(CSRC)/artn_gates_adjoint_kernel.h $(PAULI_SRCS)
 WGATE_SRCS := $(CSRC)/artn_wgate.hip $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
 KRYLOV_SRCS := $(CSRC)/artn_krylov.hip $(CSRC)/artn_krylov_kernel.h $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
 # (the single-translation-unit builds below: artn_unity.hip includes every unit source)

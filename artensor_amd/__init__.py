@@ -95,6 +95,14 @@ from .gates import (  # noqa: F401
     merge_gates,
     run_circuit,
 )
+from . import gate_adjoint  # noqa: F401
+from .gate_adjoint import (  # noqa: F401
+    GatePairCircuit,
+    apply_gates_pair_,
+    gate_adjoint_gradient,
+    gate_adjoint_info,
+    parametric_gate,
+)
 from . import wide_gates  # noqa: F401
 from .wide_gates import (  # noqa: F401
     FusedCircuit,

@@ -177,6 +177,23 @@ GATES_MAX_RANK = 4
 GATE_DIAGONAL, GATE_LOCAL = 1, 2
 
 
+class ArtnGatesAdjointInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_runs", ctypes.c_int32),
+        ("n_launches", ctypes.c_int32),
+        ("max_rank", ctypes.c_int32),
+        ("n_measured", ctypes.c_int32),
+        ("table_bytes", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
+GATES_ADJOINT_MAX_RANK = 3
+GATES_ADJOINT_GATE_BYTES = 592
+
+
 class ArtnWgateInfo(ctypes.Structure):
     _fields_ = [
         ("k", ctypes.c_int32),
@@ -314,6 +331,17 @@ _EXPORTS = {
     "artn_gates_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_void_p]),
+    # additive to ABI 9 as well: the same circuits on two states with transition elements (has("artn_gates_adjoint"))
+    "artn_gates_adjoint_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                ctypes.POINTER(ArtnGatesAdjointInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_gates_adjoint_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                               ctypes.c_int64]),
+    "artn_gates_adjoint": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     # additive to ABI 9 as well: one dense gate on one to five qubits, in place (has("artn_wgate_apply"))
     "artn_wgate_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.POINTER(ArtnWgateInfo), ctypes.c_void_p, ctypes.c_void_p]),

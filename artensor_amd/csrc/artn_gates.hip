@@ -1,4 +1,5 @@
-// artn_gates.hip -- host half of the dense-gate entry points of include/artn.h (kernels: artn_gates_kernel.h).
+// artn_gates.hip -- host half of the dense-gate entry points of include/artn.h (kernels: artn_gates_kernel.h; the same circuits on
+// two states with transition elements: artn_gates_adjoint_kernel.h).
 //
 // A translation unit of its own (build/obj/gates.o).
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 
 #include "artn_host.h"
 #include "artn_gates_kernel.h"
+#include "artn_gates_adjoint_kernel.h"
 
 struct GatesRunPlan {
   int64_t first = 0, count = 0;
@@ -133,6 +135,53 @@ static int gates_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t
   return ARTN_OK;
 }
 
+// the header and the run records of a table (include/artn.h: TABLE)
+static void gates_fill_runs(const GatesPlan &gp, ArtnGatesHeader *h, ArtnGatesRun *runs) {
+  *h = ArtnGatesHeader{(uint64_t)gp.runs.size(), (uint64_t)gp.k.size(), (uint64_t)gp.info.max_rank, 0};
+  for (size_t r = 0; r < gp.runs.size(); ++r) {
+    const GatesRunPlan &rp = gp.runs[r];
+    ArtnGatesRun rec = {};
+    rec.first = (uint64_t)rp.first, rec.count = (uint64_t)rp.count, rec.rank = (uint64_t)rp.pivot.size();
+    for (size_t j = 0; j < rp.pivot.size(); ++j) rec.pivot[j] = (uint64_t)rp.pivot[j];
+    runs[r] = rec;
+  }
+}
+
+// the record of gate g
+static ArtnGatesGate gates_fill_gate(const GatesPlan &gp, int64_t g, const double *mat) {
+  ArtnGatesGate rec = {};
+  const int kg = gp.k[g], rows = 1 << kg;
+  const GatesRunPlan &rp = gp.runs[gp.run_of[g]];
+  rec.k = (uint64_t)kg, rec.flags = (uint64_t)gp.flags[g];
+  for (int j = 0; j < kg; ++j) { // T_j: the LAST listed target first
+    const int b = gp.bits[2 * g + (kg - 1 - j)];
+    rec.bit[j] = (uint64_t)b;
+    rec.lo[j] = b < ARTN_PAULI_TILE_BITS ? (uint64_t)1 << b : 0;
+    for (size_t p = 0; p < rp.pivot.size(); ++p)
+      if (rp.pivot[p] == b) rec.slot[j] = (uint64_t)1 << p;
+  }
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < rows; ++c) rec.m[r][c][0] = mat[32 * g + 2 * (r * rows + c)], rec.m[r][c][1] = mat[32 * g + 2 * (r * rows + c) + 1];
+  return rec;
+}
+
+// the per-gate and per-run arrays of a query (any may be null)
+static void gates_report(const GatesPlan &gp, int32_t *bits, int32_t *run, int32_t *slot_mask, int32_t *local, int32_t *run_rank,
+                         int32_t *run_pivot) {
+  const int64_t n_gates = (int64_t)gp.k.size();
+  if (bits) std::copy(gp.bits.begin(), gp.bits.end(), bits);
+  if (run) std::copy(gp.run_of.begin(), gp.run_of.end(), run);
+  if (slot_mask) std::copy(gp.slot_mask.begin(), gp.slot_mask.end(), slot_mask);
+  if (local)
+    for (int64_t g = 0; g < n_gates; ++g) local[g] = (gp.flags[g] & ARTN_GATE_LOCAL) ? 1 : 0;
+  for (size_t r = 0; r < gp.runs.size(); ++r) {
+    const GatesRunPlan &rp = gp.runs[r];
+    if (run_rank) run_rank[r] = (int32_t)rp.pivot.size();
+    if (run_pivot)
+      for (size_t j = 0; j < ARTN_GATES_MAX_RANK; ++j) run_pivot[r * ARTN_GATES_MAX_RANK + j] = j < rp.pivot.size() ? rp.pivot[j] : -1;
+  }
+}
+
 template <typename T, int R>
 static hipError_t gates_launch_rank(T *a, long tiles, const ArtnGatesRun *run, const ArtnGatesGate *gates, hipStream_t st) {
   const size_t lds = ((size_t)sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
@@ -178,17 +227,7 @@ int artn_gates_query(const ArtnMarginalDesc *d, const int32_t *k, const int32_t 
   GatesPlan gp;
   if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, gp)) return rc;
   *info = gp.info;
-  if (bits) std::copy(gp.bits.begin(), gp.bits.end(), bits);
-  if (run) std::copy(gp.run_of.begin(), gp.run_of.end(), run);
-  if (slot_mask) std::copy(gp.slot_mask.begin(), gp.slot_mask.end(), slot_mask);
-  if (local)
-    for (int64_t g = 0; g < n_gates; ++g) local[g] = (gp.flags[g] & ARTN_GATE_LOCAL) ? 1 : 0;
-  for (size_t r = 0; r < gp.runs.size(); ++r) {
-    const GatesRunPlan &rp = gp.runs[r];
-    if (run_rank) run_rank[r] = (int32_t)rp.pivot.size();
-    if (run_pivot)
-      for (size_t j = 0; j < ARTN_GATES_MAX_RANK; ++j) run_pivot[r * ARTN_GATES_MAX_RANK + j] = j < rp.pivot.size() ? rp.pivot[j] : -1;
-  }
+  gates_report(gp, bits, run, slot_mask, local, run_rank, run_pivot);
   return ARTN_OK;
 }
 
@@ -203,30 +242,8 @@ int artn_gates_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *
   ArtnGatesHeader *h = (ArtnGatesHeader *)table;
   ArtnGatesRun *runs = (ArtnGatesRun *)(h + 1);
   ArtnGatesGate *gates = (ArtnGatesGate *)(runs + gp.runs.size());
-  *h = ArtnGatesHeader{(uint64_t)gp.runs.size(), (uint64_t)n_gates, (uint64_t)gp.info.max_rank, 0};
-  for (size_t r = 0; r < gp.runs.size(); ++r) {
-    const GatesRunPlan &rp = gp.runs[r];
-    ArtnGatesRun rec = {};
-    rec.first = (uint64_t)rp.first, rec.count = (uint64_t)rp.count, rec.rank = (uint64_t)rp.pivot.size();
-    for (size_t j = 0; j < rp.pivot.size(); ++j) rec.pivot[j] = (uint64_t)rp.pivot[j];
-    runs[r] = rec;
-  }
-  for (int64_t g = 0; g < n_gates; ++g) {
-    ArtnGatesGate rec = {};
-    const int kg = gp.k[g], rows = 1 << kg;
-    const GatesRunPlan &rp = gp.runs[gp.run_of[g]];
-    rec.k = (uint64_t)kg, rec.flags = (uint64_t)gp.flags[g];
-    for (int j = 0; j < kg; ++j) { // T_j: the LAST listed target first
-      const int b = gp.bits[2 * g + (kg - 1 - j)];
-      rec.bit[j] = (uint64_t)b;
-      rec.lo[j] = b < ARTN_PAULI_TILE_BITS ? (uint64_t)1 << b : 0;
-      for (size_t p = 0; p < rp.pivot.size(); ++p)
-        if (rp.pivot[p] == b) rec.slot[j] = (uint64_t)1 << p;
-    }
-    for (int r = 0; r < rows; ++r)
-      for (int c = 0; c < rows; ++c) rec.m[r][c][0] = mat[32 * g + 2 * (r * rows + c)], rec.m[r][c][1] = mat[32 * g + 2 * (r * rows + c) + 1];
-    gates[g] = rec;
-  }
+  gates_fill_runs(gp, h, runs);
+  for (int64_t g = 0; g < n_gates; ++g) gates[g] = gates_fill_gate(gp, g, mat);
   return ARTN_OK;
 }
 
@@ -242,6 +259,157 @@ int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) HIP_TRY(gates_launch(gp, (float2 *)a, table, st));
   else HIP_TRY(gates_launch(gp, (double2 *)a, table, st));
+  HIP_TRY(hipGetLastError());
+  return ARTN_OK;
+}
+
+} // extern "C"
+
+// The same circuits on two states with transition elements (include/artn.h: GATE ADJOINT; kernels: artn_gates_adjoint_kernel.h).
+// The plan is gates_plan at the two-state rank; only the limits, the measure, the byte counts and the workspace are the adjoint's own.
+struct GatesAdjointPlan {
+  GatesPlan gp;
+  std::vector<uint8_t> flag, diag; // per gate: measured; its M is diagonal
+  ArtnGatesAdjointInfo info = {};
+};
+
+// `mat` and the measure may be null (artn_gates_adjoint: they are in the table).
+static int gates_adjoint_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat, const double *measure_mat,
+                              const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank, GatesAdjointPlan &ap) {
+  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
+  const int lib_max = d->dtype == ARTN_C128 ? ARTN_GATES_ADJOINT_MAX_RANK - 1 : ARTN_GATES_ADJOINT_MAX_RANK;
+  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
+  if (max_rank > lib_max && (d->dtype == ARTN_C64 || d->dtype == ARTN_C128))
+    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the two-state maximum " + std::to_string(lib_max) + " of this dtype");
+  if (int rc = gates_plan(d, k, dims, mat, n_gates, std::min<int32_t>(max_rank < 0 ? lib_max - 1 : max_rank, lib_max), ap.gp)) return rc;
+  const GatesPlan &gp = ap.gp;
+  ap.flag.assign(n_gates, 0), ap.diag.assign(n_gates, 0);
+  int64_t flagged = 0;
+  for (int64_t g = 0; measure_flag && g < n_gates; ++g) {
+    if (!measure_flag[g]) continue;
+    if (!measure_mat) return fail(ARTN_E_INVALID, "null measure_mat with a flagged gate");
+    const int rows = 1 << gp.k[g];
+    const double *m = measure_mat + 32 * g;
+    bool diagonal = true;
+    for (int e = 0; e < 2 * rows * rows; ++e) {
+      if (!std::isfinite(m[e])) return fail(ARTN_E_INVALID, "gate " + std::to_string(g) + ": an entry of the measure matrix is not finite");
+      if (m[e] != 0.0 && (e / 2) / rows != (e / 2) % rows) diagonal = false;
+    }
+    ap.flag[g] = 1, ap.diag[g] = diagonal, ++flagged;
+  }
+  const int64_t groups = std::min<int64_t>(std::max<int64_t>(gp.n >> ARTN_PAULI_TILE_BITS, 1), ARTN_GATES_MAX_GRID);
+  ap.info = ArtnGatesAdjointInfo{};
+  ap.info.n_runs = gp.info.n_runs;
+  ap.info.n_launches = gp.info.n_runs + 1;
+  ap.info.max_rank = gp.info.max_rank;
+  ap.info.n_measured = (int32_t)flagged;
+  ap.info.table_bytes = (int64_t)sizeof(ArtnGatesHeader) + (int64_t)gp.runs.size() * (int64_t)sizeof(ArtnGatesRun) +
+                        n_gates * (int64_t)sizeof(ArtnGatesAdjointGate);
+  ap.info.workspace_bytes = n_gates * groups * ARTN_PAULI_ADJOINT_WAVES * 2 * (int64_t)sizeof(double);
+  ap.info.bytes_read = 2 * gp.info.bytes_read;
+  ap.info.bytes_written = 2 * gp.info.bytes_written;
+  return ARTN_OK;
+}
+
+template <typename T, int R>
+static hipError_t gates_adjoint_launch_rank(T *lam, T *phi, long tiles, const ArtnGatesRun *run, const ArtnGatesAdjointGate *gates, double *ws,
+                                            long groups, hipStream_t st) {
+  const size_t lds = ((size_t)2 * sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
+  if (hipError_t e = ensure_lds<artn_k_gates_adjoint<T, R>>(lds); e != hipSuccess) return e;
+  const long n_blocks = tiles >> R;
+  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_GATES_MAX_GRID)); // (at most `groups`: the workspace slots of a gate)
+  hipLaunchKernelGGL((artn_k_gates_adjoint<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, lam, phi, n_blocks, run, gates, ws, groups);
+  return hipSuccess;
+}
+
+template <typename T>
+static hipError_t gates_adjoint_launch(const GatesPlan &gp, T *lam, T *phi, const void *table, double *ws, double *out, hipStream_t st) {
+  const ArtnGatesRun *runs = (const ArtnGatesRun *)((const ArtnGatesHeader *)table + 1);
+  const ArtnGatesAdjointGate *gates = (const ArtnGatesAdjointGate *)(runs + gp.runs.size());
+  const int n_gates = (int)gp.k.size();
+  const long tiles = (long)std::max<int64_t>(gp.n >> ARTN_PAULI_TILE_BITS, 1);
+  const long groups = std::min<long>(tiles, ARTN_GATES_MAX_GRID);
+  if (gp.n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
+    hipLaunchKernelGGL(artn_k_gates_adjoint_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, lam, phi, (long)gp.n, gates, n_gates, ws);
+  } else {
+    for (size_t r = 0; r < gp.runs.size(); ++r) {
+      hipError_t e = hipErrorInvalidValue;
+      switch ((int)gp.runs[r].pivot.size()) {
+      case 0: e = gates_adjoint_launch_rank<T, 0>(lam, phi, tiles, runs + r, gates, ws, groups, st); break;
+      case 1: e = gates_adjoint_launch_rank<T, 1>(lam, phi, tiles, runs + r, gates, ws, groups, st); break;
+      case 2: e = gates_adjoint_launch_rank<T, 2>(lam, phi, tiles, runs + r, gates, ws, groups, st); break;
+      case 3:
+        if constexpr (sizeof(T) == 8) e = gates_adjoint_launch_rank<T, 3>(lam, phi, tiles, runs + r, gates, ws, groups, st);
+        break;
+      }
+      if (e != hipSuccess) return e;
+    }
+  }
+  hipLaunchKernelGGL(artn_k_gates_adjoint_finish, dim3((unsigned)n_gates), dim3(ARTN_BORN_THREADS), 0, st, (const double *)ws, groups, tiles,
+                     gates, out);
+  return hipSuccess;
+}
+
+extern "C" {
+
+int artn_gates_adjoint_query(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat,
+                             const double *measure_mat, const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank,
+                             ArtnGatesAdjointInfo *info, int32_t *bits, int32_t *run, int32_t *slot_mask, int32_t *local,
+                             int32_t *run_rank, int32_t *run_pivot) {
+  if (!info) return fail(ARTN_E_INVALID, "null info");
+  if (!mat) return fail(ARTN_E_INVALID, "null pointer");
+  GatesAdjointPlan ap;
+  if (int rc = gates_adjoint_plan(d, k, dims, mat, measure_mat, measure_flag, n_gates, max_rank, ap)) return rc;
+  *info = ap.info;
+  gates_report(ap.gp, bits, run, slot_mask, local, run_rank, run_pivot);
+  return ARTN_OK;
+}
+
+int artn_gates_adjoint_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat,
+                            const double *measure_mat, const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank, void *table,
+                            int64_t table_bytes) {
+  if (!mat) return fail(ARTN_E_INVALID, "null pointer");
+  GatesAdjointPlan ap;
+  if (int rc = gates_adjoint_plan(d, k, dims, mat, measure_mat, measure_flag, n_gates, max_rank, ap)) return rc;
+  if (!table) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_gates_adjoint_query reports");
+  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint_pack needs an 8-byte aligned table");
+  const GatesPlan &gp = ap.gp;
+  ArtnGatesHeader *h = (ArtnGatesHeader *)table;
+  ArtnGatesRun *runs = (ArtnGatesRun *)(h + 1);
+  ArtnGatesAdjointGate *gates = (ArtnGatesAdjointGate *)(runs + gp.runs.size());
+  gates_fill_runs(gp, h, runs);
+  for (int64_t g = 0; g < n_gates; ++g) {
+    ArtnGatesAdjointGate rec = {};
+    rec.g = gates_fill_gate(gp, g, mat);
+    const int rows = 1 << gp.k[g];
+    if (ap.flag[g])
+      for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < rows; ++c)
+          rec.mm[r][c][0] = measure_mat[32 * g + 2 * (r * rows + c)], rec.mm[r][c][1] = measure_mat[32 * g + 2 * (r * rows + c) + 1];
+    rec.measure = (uint64_t)ap.flag[g] | (uint64_t)ap.diag[g] << 1 | (uint64_t)gp.runs[gp.run_of[g]].pivot.size() << 8;
+    gates[g] = rec;
+  }
+  return ARTN_OK;
+}
+
+int artn_gates_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const int32_t *k, const int32_t *dims, int64_t n_gates,
+                       int32_t max_rank, const void *table, int64_t table_bytes, void *workspace, int64_t workspace_bytes,
+                       double *out, void *stream) {
+  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
+  GatesAdjointPlan ap;
+  if (int rc = gates_adjoint_plan(d, k, dims, nullptr, nullptr, nullptr, n_gates, max_rank, ap)) return rc; // (matrices and flags are in the table)
+  if (!lam || !phi || !table || !workspace || !out) return fail(ARTN_E_INVALID, "null pointer");
+  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_gates_adjoint_query reports");
+  if (workspace_bytes < ap.info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_gates_adjoint_query reports");
+  if ((((uintptr_t)lam | (uintptr_t)phi | (uintptr_t)workspace) & 15) != 0)
+    return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint needs 16-byte aligned arrays and workspace");
+  if ((((uintptr_t)table | (uintptr_t)out) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint needs an 8-byte aligned table and output");
+  const uintptr_t bytes = (uintptr_t)ap.gp.n * (d->dtype == ARTN_C64 ? 8 : 16), pl = (uintptr_t)lam, pp = (uintptr_t)phi;
+  if (pl < pp + bytes && pp < pl + bytes) return fail(ARTN_E_INVALID, "artn_gates_adjoint: lam overlaps phi");
+  hipStream_t st = (hipStream_t)stream;
+  if (d->dtype == ARTN_C64) HIP_TRY(gates_adjoint_launch(ap.gp, (float2 *)lam, (float2 *)phi, table, (double *)workspace, out, st));
+  else HIP_TRY(gates_adjoint_launch(ap.gp, (double2 *)lam, (double2 *)phi, table, (double *)workspace, out, st));
   HIP_TRY(hipGetLastError());
   return ARTN_OK;
 }

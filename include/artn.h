@@ -643,6 +643,70 @@ int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const
                      int32_t max_rank, const void *table, int64_t table_bytes, void *stream);
 
 /*
+ * GATE ADJOINT: the same circuits on TWO arrays with transition elements (additive to ABI 9: look the symbols up before calling).
+ * `lam` and `phi` share one descriptor (shape, strides, dtype).  Gates, dims and mat are those of artn_gates_query.  For every
+ * gate g of the circuit, in order:
+ *     1. when the gate is flagged in `measure_flag` (uint8 [n_gates], non-zero = flagged; NULL flags no gate),
+ *            t_g = sum_i conj(lam[i]) * (M_g phi)[i]
+ *        with the matrix measure_mat[g] (float64 [n_gates][32], laid out as mat; any matrix of the gate's size; read for the
+ *        flagged gates only, so measure_mat may be NULL when no gate is flagged), on the dims of the gate and on the two arrays as
+ *        they are immediately before gate g.  (M phi)[i] is formed by the ARITHMETIC of artn_gates_apply with the coefficients of
+ *        M -- float64, d = 2^k - 1 .. 0, the products of an exactly zero component left out -- and is NOT rounded to the dtype;
+ *        conj(lam[i]) (M phi)[i] is formed in float64 with one rounding per Re and Im; partial sums are added in a fixed
+ *        order -- no atomics, bit-identical from run to run for one plan.  The order follows the blocks of the run, so t_g may
+ *        differ in the last bits between max_rank values.  out[g] = Re t_g, Im t_g; 0, 0 for a gate that is not flagged;
+ *     2. gate g is applied to phi and to lam: each array ends bit for bit as artn_gates_apply leaves it alone, for every max_rank
+ *        and every measure.
+ * With lam = (U_K .. U_{k+1})^+ H phi_K, the reversed circuit of the U_k^+ and M_k = dU_k/dtheta U_k^+, dE/dtheta = 2 Re t_k.
+ *
+ * PLAN, runs, blocks, slots and pivots are those of artn_gates_query at the same effective max_rank; a workgroup holds the 2^r
+ * tiles of a block of both arrays, so the ranks lie one lower: -1 selects 2 for complex64 and 1 for complex128 (64 KiB of LDS),
+ * the maximum is ARTN_GATES_ADJOINT_MAX_RANK for complex64 and one less for complex128 (128 KiB); more is ARTN_E_UNSUPPORTED,
+ * below -1 ARTN_E_INVALID.  A two-qubit gate on two high bits opens a run of rank 2 whatever max_rank is, as there.  One launch
+ * per run, then one finish launch.  ARTN_E_INVALID also: an entry of a flagged measure_mat that is not finite.
+ *
+ * TABLE: ArtnGatesHeader, n_runs x ArtnGatesRun, then n_gates x ArtnGatesAdjointGate, 592 bytes each: the ArtnGatesGate of
+ * artn_gates_pack, mm[4][4][2] = M[r][c] as float64 (Re, Im), zero for a gate that is not flagged, and the `measure` word:
+ *     bit 0   1 when the gate is measured      bit 1   1 when M is diagonal      bits 8..15   the rank of the gate's run
+ * table_bytes = 32 + 64 * n_runs + 592 * n_gates.
+ * WORKSPACE (device, 16-byte aligned): float64 [n_gates][G][4][2], G = min(max(n >> 10, 1), 2048) -- per gate, workgroup and wave
+ * the Re and Im of a partial sum, written by plain stores; workspace_bytes = 64 * G * n_gates.  Needs no initialisation.
+ */
+#define ARTN_GATES_ADJOINT_MAX_RANK 3
+typedef struct ArtnGatesAdjointGate {
+  ArtnGatesGate g;
+  double mm[4][4][2];
+  uint64_t measure, reserved;
+} ArtnGatesAdjointGate;
+typedef struct ArtnGatesAdjointInfo {
+  int32_t n_runs;          /* = the launches before the finish launch                */
+  int32_t n_launches;      /* n_runs + 1                                             */
+  int32_t max_rank;        /* the effective one, as ArtnGatesInfo                    */
+  int32_t n_measured;      /* flagged gates                                          */
+  int64_t table_bytes;
+  int64_t workspace_bytes;
+  int64_t bytes_read;      /* 2 * n_runs * n * element size                          */
+  int64_t bytes_written;   /* the same                                               */
+} ArtnGatesAdjointInfo;
+/* Host-only: as artn_gates_query (the same per-gate and per-run arrays, run_pivot [.][4]) at the two-state ranks. */
+int artn_gates_adjoint_query(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat,
+                             const double *measure_mat, const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank,
+                             ArtnGatesAdjointInfo *info, int32_t *bits, int32_t *run, int32_t *slot_mask, int32_t *local,
+                             int32_t *run_rank, int32_t *run_pivot);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query with the same max_rank). */
+int artn_gates_adjoint_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat,
+                            const double *measure_mat, const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank, void *table,
+                            int64_t table_bytes);
+/* The circuit on `lam` and `phi`, in place, and out[n_gates][2] (device, 8-byte aligned), on `stream`.  `table` is DEVICE memory
+ * holding what artn_gates_adjoint_pack wrote for the same descriptor, k, dims, n_gates and max_rank (8-byte aligned).
+ * ARTN_E_INVALID: a null pointer, table_bytes or workspace_bytes below the query's, byte ranges of lam and phi that overlap;
+ * ARTN_E_UNSUPPORTED: lam, phi or workspace not 16-byte aligned.  No allocation, copy or synchronisation.  ARTN_E_NODEVICE
+ * without a device. */
+int artn_gates_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const int32_t *k, const int32_t *dims, int64_t n_gates,
+                       int32_t max_rank, const void *table, int64_t table_bytes, void *workspace, int64_t workspace_bytes,
+                       double *out, void *stream);
+
+/*
  * ONE dense gate on one to five qubits, in place, in one launch (additive to ABI 9: look the symbols up before calling).  The
  * gate acts on k (1..5) distinct dimensions of extent 2, dims[0 .. k-1], with the matrix mat (float64 [2 * 4^k]: the 2^k x 2^k
  * matrix row-major, Re and Im interleaved).  Any matrix, unitary or not.  The convention is that of artn_gates_*: the FIRST
