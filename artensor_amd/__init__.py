@@ -122,6 +122,14 @@ from .krylov import (  # noqa: F401
     lanczos,
     lanczos_ground_state,
 )
+from . import measure  # noqa: F401
+from .measure import (  # noqa: F401
+    apply_channel_,
+    measure_,
+    measure_info,
+    postselect_,
+    reset_,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

@@ -231,6 +231,25 @@ class ArtnKrylovInfo(ctypes.Structure):
     ]
 
 
+MEASURE_MAX_DIMS = 10
+MEASURE_RECORD_BYTES = 32
+
+
+class ArtnMeasureInfo(ctypes.Structure):
+    _fields_ = [
+        ("k", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("collapse_launches", ctypes.c_int32),
+        ("reset_launches", ctypes.c_int32),
+        ("dim", ctypes.c_int64),
+        ("n", ctypes.c_int64),
+        ("record_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+        ("mem_bit", ctypes.c_int32 * MEASURE_MAX_DIMS),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -355,6 +374,12 @@ _EXPORTS = {
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "artn_krylov_combine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    # additive to ABI 9 as well: measurement, post-selection and reset in place (has("artn_measure_collapse"))
+    "artn_measure_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.POINTER(ArtnMeasureInfo)]),
+    "artn_measure_choose": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_measure_collapse": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_void_p]),
 }
 
 

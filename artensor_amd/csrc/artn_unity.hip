@@ -24,3 +24,4 @@
 #include "artn_gates.hip" // (artn_gates_kernel.h, artn_gates_adjoint_kernel.h)
 #include "artn_wgate.hip" // (artn_wgate_kernel.h)
 #include "artn_krylov.hip" // (artn_krylov_kernel.h)
+#include "artn_measure.hip" // (artn_measure_kernel.h)

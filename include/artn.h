@@ -820,6 +820,53 @@ int artn_krylov_dots(const void *const *vecs, int32_t m, const void *w, int64_t 
 int artn_krylov_combine(void *y, const double *coeff, const void *const *xs, int32_t m, int64_t n, int32_t dtype, void *ws,
                         int64_t ws_bytes, double *out4, void *stream);
 
+/* ---- projective measurement, post-selection and reset, in place (additive to ABI 9: has("artn_measure_collapse")) -------------
+ * The state is a DENSE tensor of power-of-two extents in DEVICE memory, 16-byte aligned (descriptor, density checks and size
+ * limits of artn_pauli_query).  The dimensions with keep[] != 0 are the MEASURED ones, 1 to ARTN_MEASURE_MAX_DIMS of them, each of
+ * extent 2; an outcome is the integer whose most significant digit is the first of them in the descriptor's order (the convention
+ * of artn_rdm), D = 2^k outcomes.  A measured dimension of stride 2^b is bit b of the flat memory index.
+ *
+ * artn_measure_choose: one small launch.  q (DEVICE, D float64, what artn_marginal writes for the same descriptor) and `uniform`
+ *   (DEVICE, one float64 in [0, 1); may be NULL where forced_outcome >= 0) give the record (DEVICE, 32 bytes, 8-byte aligned):
+ *       int64 outcome; float64 probability, total, scale;
+ *   total = q[0] + q[1] + ... in ascending order.  forced_outcome < 0: the outcome is the smallest o whose inclusive running sum
+ *   (the same additions) exceeds uniform * total, or the last o with q[o] > 0 where rounding leaves none; an o with q[o] == 0 is
+ *   never chosen.  forced_outcome >= 0: that outcome (post-selection).  probability = q[o] / total; scale = sqrt(total / q[o])
+ *   where renormalize != 0, else 1.  Where total is not finite, total is not > 0 or the forced q[o] is not > 0, nothing can be
+ *   observed: outcome = -1, probability = 0, scale = 1.
+ * artn_measure_collapse: reads the record from DEVICE memory.  Outcome -1 leaves the state untouched bit for bit.  Otherwise every
+ *   element whose measured digits differ from the outcome becomes +0.0 in both components -- written, never read, so -0.0,
+ *   denormals and non-finite values there vanish -- and every kept component c becomes fl(float64(c) * scale), one rounding;
+ *   under scale == 1 kept elements are unchanged bit for bit.  reset != 0: the kept element a[r, o] * scale lands at [r, 0..0]
+ *   instead and every other element becomes +0.0 (two launches: a move that reads only elements with digits o and writes only
+ *   elements with digits 0 -- and +0.0 to the second half of a 16-byte vector it stores, where memory bit 0 of complex64 is
+ *   measured -- then a zero-fill of everything else; the result does not depend on scheduling, no buffer is used).
+ *   One streaming launch (reset: two) over memory order, 16 bytes per lane, plain stores, no atomics.
+ * Both run on `stream` and do no allocation, copy or synchronisation.
+ * ARTN_E_INVALID: a null pointer, a layout that is not dense, a measured dimension whose extent is not 2, none or more than
+ * ARTN_MEASURE_MAX_DIMS of them, D < 1.  ARTN_E_UNSUPPORTED: another dtype, an extent that is no power of two, more than 96
+ * dimensions or 2^40 elements, a state that is not 16-byte aligned or a record that is not 8-byte aligned.  ARTN_E_NODEVICE
+ * without a device (the query is host-only). */
+#define ARTN_MEASURE_MAX_DIMS 10
+#define ARTN_MEASURE_RECORD_BYTES 32
+typedef struct ArtnMeasureInfo {
+  int32_t k;                 /* measured dimensions                                                              */
+  int32_t grid;              /* workgroups of a streaming launch                                                 */
+  int32_t collapse_launches; /* 1                                                                                */
+  int32_t reset_launches;    /* 2: move, clear                                                                   */
+  int64_t dim;               /* D = 2^k outcomes                                                                 */
+  int64_t n;                 /* elements of the state                                                            */
+  int64_t record_bytes;      /* ARTN_MEASURE_RECORD_BYTES                                                        */
+  int64_t bytes_read;        /* nominal, collapse and reset alike: the n / D kept elements                       */
+  int64_t bytes_written;     /* nominal, collapse and reset alike: all n elements                                */
+  int32_t mem_bit[ARTN_MEASURE_MAX_DIMS]; /* memory bit of measured dimension j, in listed order; the rest -1    */
+} ArtnMeasureInfo;
+/* Host-only: validates the layout and the measured dimensions, reports the plan. */
+int artn_measure_query(const ArtnMarginalDesc *d, ArtnMeasureInfo *info);
+int artn_measure_choose(const double *q, int64_t D, const double *uniform, int64_t forced_outcome, int32_t renormalize, void *record,
+                        void *stream);
+int artn_measure_collapse(const ArtnMarginalDesc *d, void *a, const void *record, int32_t reset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
