@@ -8,23 +8,26 @@ all: $(LIB)
 
 # Nineteen objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit),
 # artn_born.hip, artn_rdm.hip, artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_krylov.hip, artn_measure.hip, and the eleven few-line sources under units/, each of which defines one artn_launch_*() and so
-# emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by all of them):
+# emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by all of them).  Two headers
+# belong to no single object: artn_state_host.h (born, rdm, pauli, gates, wgate, measure) and artn_block_kernel.h (pauli, gates):
 # `make -j8` builds in about a minute and a half instead of four.
 HOST_HDRS := $(CSRC)/artn_host.h include/artn.h
+# (the operations on a dense amplitude array: shared host checks, and the block skeleton of the four run kernels)
+STATE_HDRS := $(CSRC)/artn_state_host.h $(HOST_HDRS)
 HDRS := $(HOST_HDRS) $(CSRC)/artn_kernels.hip $(CSRC)/artn_wide_kernel.h $(CSRC)/artn_plan.h $(CSRC)/artn_xgemm_plan.h
 LAUNCH_HDRS := $(CSRC)/artn_launch_bits.h $(CSRC)/artn_launch_bits128.h $(CSRC)/artn_launch_bits3.h \
                $(CSRC)/artn_bits128_kernel.h $(CSRC)/artn_bits3_kernel.h
 MAIN_HDRS := $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/artn_pgemm_kernel.h $(CSRC)/artn_xgemm_kernel.h \
              $(CSRC)/artn_xgemm128_kernel.h $(CSRC)/artn_xrow_kernel.h $(CSRC)/artn_xgemm_pc_kernel.h
-BORN_SRCS := $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
-RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(HOST_HDRS)
+BORN_SRCS := $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
+RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(STATE_HDRS)
 PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pauli_apply_kernel.h $(CSRC)/artn_pauli_evolve_kernel.h \
-              $(CSRC)/artn_pauli_adjoint_kernel.h \
-              $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
+              $(CSRC)/artn_pauli_adjoint_kernel.h $(CSRC)/artn_block_kernel.h \
+              $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
 GATES_SRCS := $(CSRC)/artn_gates.hip $(CSRC)/artn_gates_kernel.h $(CSRC)/artn_gates_adjoint_kernel.h $(PAULI_SRCS)
 WGATE_SRCS := $(CSRC)/artn_wgate.hip $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
 KRYLOV_SRCS := $(CSRC)/artn_krylov.hip $(CSRC)/artn_krylov_kernel.h $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
-MEASURE_SRCS := $(CSRC)/artn_measure.hip $(CSRC)/artn_measure_kernel.h $(HOST_HDRS)
+MEASURE_SRCS := $(CSRC)/artn_measure.hip $(CSRC)/artn_measure_kernel.h $(STATE_HDRS)
 # (the single-translation-unit builds below: artn_unity.hip includes every unit source)
 SRCS := $(CSRC)/artn_unity.hip $(CSRC)/artn_api.hip $(wildcard $(CSRC)/units/*.hip) $(HDRS) $(LAUNCH_HDRS) $(MAIN_HDRS) $(BORN_SRCS) $(RDM_SRCS) $(PAULI_SRCS) $(GATES_SRCS) $(WGATE_SRCS) $(KRYLOV_SRCS) $(MEASURE_SRCS)
 OBJDIR := build/obj

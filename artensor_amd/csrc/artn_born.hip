@@ -7,19 +7,14 @@
 #include <vector>
 
 #include "artn_host.h"
+#include "artn_state_host.h"
 #include "artn_born_kernel.h"
-
-static int born_ceil_log2(int64_t n) {
-  int b = 0;
-  while (b < 62 && ((int64_t)1 << b) < n) ++b;
-  return b;
-}
 
 static int born_plan(int64_t n, int32_t dtype, ArtnBornPlan *p) {
   if (!p) return fail(ARTN_E_INVALID, "null plan");
   if (n < 1 || n > ((int64_t)1 << 40)) return fail(ARTN_E_INVALID, "element count out of range");
   if (dtype != ARTN_C64 && dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "Born statistics take complex64 or complex128");
-  p->block_bits = std::min(ARTN_BORN_MAX_BLOCK_BITS, std::max(ARTN_BORN_MIN_BLOCK_BITS, born_ceil_log2(n) - 16));
+  p->block_bits = std::min(ARTN_BORN_MAX_BLOCK_BITS, std::max(ARTN_BORN_MIN_BLOCK_BITS, state_ceil_log2(n) - 16));
   p->n_blocks = (n + ((int64_t)1 << p->block_bits) - 1) >> p->block_bits;
   const int64_t tiles = (n + 4 * ARTN_BORN_THREADS - 1) / (4 * ARTN_BORN_THREADS);
   p->overlap_grid = (int32_t)std::min<int64_t>(tiles, ARTN_BORN_MAX_GRID);
@@ -27,33 +22,20 @@ static int born_plan(int64_t n, int32_t dtype, ArtnBornPlan *p) {
   return ARTN_OK;
 }
 
-// (dense: sorted by stride, every stride is the product of the extents below it)
+// (the layout checks: artn_state_host.h)
 static int marg_plan(const ArtnMarginalDesc *d, ArtnMarginalInfo *info, ArtnMargStream *sp, ArtnMargGeneric *gp) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (d->dtype != ARTN_C64 && d->dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "marginals take complex64 or complex128");
-  if (d->n_dims < 0 || d->n_dims > ARTN_MARG_MAX_DIMS) return fail(ARTN_E_INVALID, "bad number of dimensions");
-  std::vector<int> order;
-  bool pow2 = true;
-  for (int i = 0; i < d->n_dims; ++i) {
-    if (d->extent[i] < 1) return fail(ARTN_E_INVALID, "extent below 1");
-    if (d->extent[i] == 1) continue; // (carries no index)
-    if (d->stride[i] < 1) return fail(ARTN_E_INVALID, "the tensor is not dense: stride below 1");
-    if (d->extent[i] & (d->extent[i] - 1)) pow2 = false;
-    order.push_back(i);
-  }
-  std::sort(order.begin(), order.end(), [&](int x, int y) { return d->stride[x] < d->stride[y]; });
-  int64_t n = 1;
-  for (int i : order) {
-    if (d->stride[i] != n) return fail(ARTN_E_INVALID, "the tensor is not dense: its strides overlap or leave gaps");
-    if (d->extent[i] > ((int64_t)1 << 40) / n) return fail(ARTN_E_INVALID, "element count out of range");
-    n *= d->extent[i];
-  }
+  if (int rc = state_desc(d, "marginals take", ARTN_MARG_MAX_DIMS, true)) return rc;
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  if (l.too_big) return fail(ARTN_E_INVALID, "element count out of range");
+  const int64_t n = l.n;
+  const bool pow2 = l.pow2;
   int64_t n_out = 1;
-  for (int i : order)
+  for (int i : l.order)
     if (d->keep[i]) n_out *= d->extent[i];
   ArtnMarginalInfo out = {};
   out.out_elems = n_out;
-  const int nbits = born_ceil_log2(n), kept_bits = born_ceil_log2(n_out);
+  const int nbits = state_ceil_log2(n), kept_bits = state_ceil_log2(n_out);
   if (pow2 && nbits >= ARTN_MARG_CHUNK_BITS && kept_bits <= ARTN_MARG_MAX_KEPT_BITS) {
     ArtnMargStream s = {};
     // memory bits of every dimension; output bits: kept dimensions in listed order, the last one fastest
@@ -62,7 +44,7 @@ static int marg_plan(const ArtnMarginalDesc *d, ArtnMarginalInfo *info, ArtnMarg
     int ob = 0;
     for (int i = d->n_dims - 1; i >= 0; --i) {
       if (d->extent[i] == 1 || !d->keep[i]) continue;
-      const int e = born_ceil_log2(d->extent[i]), s0 = born_ceil_log2(d->stride[i]);
+      const int e = state_ceil_log2(d->extent[i]), s0 = state_ceil_log2(d->stride[i]);
       for (int b = 0; b < e; ++b) {
         kmask |= (uint64_t)1 << (s0 + b);
         out_of_mem_bit[s0 + b] = ob++;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "artn_host.h"
+#include "artn_state_host.h"
 #include "artn_gates_kernel.h"
 #include "artn_gates_adjoint_kernel.h"
 
@@ -28,42 +29,16 @@ struct GatesPlan {
 // PLAN).  `mat` may be null (artn_gates_apply: the matrices are in the table); the flags are then not set.
 static int gates_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat, int64_t n_gates,
                       int32_t max_rank, GatesPlan &gp) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (d->dtype != ARTN_C64 && d->dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "gate circuits take complex64 or complex128");
-  if (d->n_dims < 0) return fail(ARTN_E_INVALID, "bad number of dimensions");
-  if (d->n_dims > ARTN_MARG_MAX_DIMS) return fail(ARTN_E_UNSUPPORTED, "gate circuits take at most 96 dimensions");
+  if (int rc = state_desc(d, "gate circuits take", ARTN_MARG_MAX_DIMS, false)) return rc;
   if (n_gates < 1) return fail(ARTN_E_INVALID, "at least one gate is needed");
   if (!k || !dims) return fail(ARTN_E_INVALID, "null pointer");
   const int nd = d->n_dims;
-  std::vector<int> order;
-  bool pow2 = true;
-  for (int i = 0; i < nd; ++i) {
-    if (d->extent[i] < 1) return fail(ARTN_E_INVALID, "extent below 1");
-    if (d->extent[i] == 1) continue; // (carries no index)
-    if (d->stride[i] < 1) return fail(ARTN_E_INVALID, "the tensor is not dense: stride below 1");
-    if (d->extent[i] & (d->extent[i] - 1)) pow2 = false;
-    order.push_back(i);
-  }
-  std::sort(order.begin(), order.end(), [&](int x, int y) { return d->stride[x] < d->stride[y]; });
-  int64_t n = 1;
-  bool too_big = false;
-  for (int i : order) {
-    if (d->stride[i] != n) return fail(ARTN_E_INVALID, "the tensor is not dense: its strides overlap or leave gaps");
-    if (d->extent[i] > ((int64_t)1 << 40) / n) {
-      too_big = true;
-      break;
-    }
-    n *= d->extent[i];
-  }
-  if (!pow2) return fail(ARTN_E_UNSUPPORTED, "gate circuits take power-of-two extents");
-  if (too_big) return fail(ARTN_E_UNSUPPORTED, "gate circuits take at most 2^40 elements");
-  gp.n = n;
-  const int lib_max = d->dtype == ARTN_C64 ? ARTN_GATES_MAX_RANK : ARTN_GATES_MAX_RANK - 1;
-  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
-  if (max_rank > lib_max)
-    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the maximum " + std::to_string(lib_max) + " of this dtype");
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  if (int rc = state_bits_only(l, "gate circuits take")) return rc;
+  const int64_t n = gp.n = l.n;
+  if (int rc = state_max_rank(d->dtype, max_rank, ARTN_GATES_MAX_RANK, false, max_rank)) return rc;
   if (n_gates > INT32_MAX) return fail(ARTN_E_UNSUPPORTED, "too many gates in one circuit");
-  if (max_rank < 0) max_rank = lib_max - 1; // 64 KiB of LDS per workgroup
   gp.k.assign(k, k + n_gates), gp.bits.assign(2 * n_gates, -1), gp.flags.assign(n_gates, 0);
   for (int64_t g = 0; g < n_gates; ++g) {
     const std::string who = "gate " + std::to_string(g) + ": ";
@@ -78,19 +53,12 @@ static int gates_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t
     }
     if (k[g] == 2 && dims[2 * g] == dims[2 * g + 1]) return fail(ARTN_E_INVALID, who + "the two dimensions must differ");
     if (!mat) continue;
-    const int rows = 1 << k[g];
-    const double *m = mat + 32 * g;
-    bool diagonal = true;
-    for (int e = 0; e < 2 * rows * rows; ++e) {
-      if (!std::isfinite(m[e])) return fail(ARTN_E_INVALID, who + "a matrix entry is not finite");
-      if (m[e] != 0.0 && (e / 2) / rows != (e / 2) % rows) diagonal = false;
-    }
+    bool diagonal;
+    if (!state_matrix_scan(mat + 32 * g, 1 << k[g], diagonal)) return fail(ARTN_E_INVALID, who + "a matrix entry is not finite");
     const bool low = gp.bits[2 * g] < 2 && gp.bits[2 * g + 1] < 2;
     gp.flags[g] = (diagonal ? ARTN_GATE_DIAGONAL : 0) | (diagonal || low ? ARTN_GATE_LOCAL : 0);
   }
-  int tile_bits = 0;
-  while (((int64_t)1 << (ARTN_PAULI_TILE_BITS + tile_bits + 1)) <= n) ++tile_bits;
-  const int cap = std::min<int>(max_rank, tile_bits);
+  const int cap = state_rank_cap(n, ARTN_PAULI_TILE_BITS, max_rank);
   gp.run_of.assign(n_gates, 0), gp.slot_mask.assign(n_gates, 0);
   GatesRunPlan cur;
   auto close = [&]() {
@@ -194,24 +162,18 @@ static hipError_t gates_launch_rank(T *a, long tiles, const ArtnGatesRun *run, c
 
 template <typename T>
 static hipError_t gates_launch(const GatesPlan &gp, T *a, const void *table, hipStream_t st) {
-  const ArtnGatesRun *runs = (const ArtnGatesRun *)((const ArtnGatesHeader *)table + 1);
-  const ArtnGatesGate *gates = (const ArtnGatesGate *)(runs + gp.runs.size());
+  const ArtnGatesRun *runs;
+  const ArtnGatesGate *gates;
+  state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
   if (gp.n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
     hipLaunchKernelGGL(artn_k_gates_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, a, (long)gp.n, gates, (int)gp.k.size());
     return hipSuccess;
   }
   const long tiles = (long)(gp.n >> ARTN_PAULI_TILE_BITS);
   for (size_t r = 0; r < gp.runs.size(); ++r) {
-    hipError_t e = hipErrorInvalidValue;
-    switch ((int)gp.runs[r].pivot.size()) {
-    case 0: e = gates_launch_rank<T, 0>(a, tiles, runs + r, gates, st); break;
-    case 1: e = gates_launch_rank<T, 1>(a, tiles, runs + r, gates, st); break;
-    case 2: e = gates_launch_rank<T, 2>(a, tiles, runs + r, gates, st); break;
-    case 3: e = gates_launch_rank<T, 3>(a, tiles, runs + r, gates, st); break;
-    case 4:
-      if constexpr (sizeof(T) == 8) e = gates_launch_rank<T, 4>(a, tiles, runs + r, gates, st);
-      break;
-    }
+    const hipError_t e = state_with_rank<T, ARTN_GATES_MAX_RANK>((int)gp.runs[r].pivot.size(), [&](auto rank) {
+      return gates_launch_rank<T, decltype(rank)::value>(a, tiles, runs + r, gates, st);
+    });
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -237,12 +199,12 @@ int artn_gates_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *
   GatesPlan gp;
   if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, gp)) return rc;
   if (!table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < gp.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_gates_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_pack needs an 8-byte aligned table");
-  ArtnGatesHeader *h = (ArtnGatesHeader *)table;
-  ArtnGatesRun *runs = (ArtnGatesRun *)(h + 1);
-  ArtnGatesGate *gates = (ArtnGatesGate *)(runs + gp.runs.size());
-  gates_fill_runs(gp, h, runs);
+  if (int rc = state_table_fits(table_bytes, gp.info.table_bytes, "artn_gates_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_gates_pack")) return rc;
+  ArtnGatesRun *runs;
+  ArtnGatesGate *gates;
+  state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
+  gates_fill_runs(gp, (ArtnGatesHeader *)table, runs);
   for (int64_t g = 0; g < n_gates; ++g) gates[g] = gates_fill_gate(gp, g, mat);
   return ARTN_OK;
 }
@@ -253,9 +215,9 @@ int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const
   GatesPlan gp;
   if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, gp)) return rc;
   if (!a || !table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < gp.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_gates_query reports");
-  if (((uintptr_t)a & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_apply needs a 16-byte aligned array");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_apply needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, gp.info.table_bytes, "artn_gates_query")) return rc;
+  if (int rc = state_array_aligned(a, "artn_gates_apply")) return rc;
+  if (int rc = state_table_aligned(table, "artn_gates_apply")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) HIP_TRY(gates_launch(gp, (float2 *)a, table, st));
   else HIP_TRY(gates_launch(gp, (double2 *)a, table, st));
@@ -277,24 +239,17 @@ struct GatesAdjointPlan {
 static int gates_adjoint_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat, const double *measure_mat,
                               const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank, GatesAdjointPlan &ap) {
   if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  const int lib_max = d->dtype == ARTN_C128 ? ARTN_GATES_ADJOINT_MAX_RANK - 1 : ARTN_GATES_ADJOINT_MAX_RANK;
-  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
-  if (max_rank > lib_max && (d->dtype == ARTN_C64 || d->dtype == ARTN_C128))
-    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the two-state maximum " + std::to_string(lib_max) + " of this dtype");
-  if (int rc = gates_plan(d, k, dims, mat, n_gates, std::min<int32_t>(max_rank < 0 ? lib_max - 1 : max_rank, lib_max), ap.gp)) return rc;
+  if (int rc = state_max_rank(d->dtype, max_rank, ARTN_GATES_ADJOINT_MAX_RANK, true, max_rank)) return rc;
+  if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, ap.gp)) return rc;
   const GatesPlan &gp = ap.gp;
   ap.flag.assign(n_gates, 0), ap.diag.assign(n_gates, 0);
   int64_t flagged = 0;
   for (int64_t g = 0; measure_flag && g < n_gates; ++g) {
     if (!measure_flag[g]) continue;
     if (!measure_mat) return fail(ARTN_E_INVALID, "null measure_mat with a flagged gate");
-    const int rows = 1 << gp.k[g];
-    const double *m = measure_mat + 32 * g;
-    bool diagonal = true;
-    for (int e = 0; e < 2 * rows * rows; ++e) {
-      if (!std::isfinite(m[e])) return fail(ARTN_E_INVALID, "gate " + std::to_string(g) + ": an entry of the measure matrix is not finite");
-      if (m[e] != 0.0 && (e / 2) / rows != (e / 2) % rows) diagonal = false;
-    }
+    bool diagonal;
+    if (!state_matrix_scan(measure_mat + 32 * g, 1 << gp.k[g], diagonal))
+      return fail(ARTN_E_INVALID, "gate " + std::to_string(g) + ": an entry of the measure matrix is not finite");
     ap.flag[g] = 1, ap.diag[g] = diagonal, ++flagged;
   }
   const int64_t groups = std::min<int64_t>(std::max<int64_t>(gp.n >> ARTN_PAULI_TILE_BITS, 1), ARTN_GATES_MAX_GRID);
@@ -324,8 +279,9 @@ static hipError_t gates_adjoint_launch_rank(T *lam, T *phi, long tiles, const Ar
 
 template <typename T>
 static hipError_t gates_adjoint_launch(const GatesPlan &gp, T *lam, T *phi, const void *table, double *ws, double *out, hipStream_t st) {
-  const ArtnGatesRun *runs = (const ArtnGatesRun *)((const ArtnGatesHeader *)table + 1);
-  const ArtnGatesAdjointGate *gates = (const ArtnGatesAdjointGate *)(runs + gp.runs.size());
+  const ArtnGatesRun *runs;
+  const ArtnGatesAdjointGate *gates;
+  state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
   const int n_gates = (int)gp.k.size();
   const long tiles = (long)std::max<int64_t>(gp.n >> ARTN_PAULI_TILE_BITS, 1);
   const long groups = std::min<long>(tiles, ARTN_GATES_MAX_GRID);
@@ -333,15 +289,9 @@ static hipError_t gates_adjoint_launch(const GatesPlan &gp, T *lam, T *phi, cons
     hipLaunchKernelGGL(artn_k_gates_adjoint_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, lam, phi, (long)gp.n, gates, n_gates, ws);
   } else {
     for (size_t r = 0; r < gp.runs.size(); ++r) {
-      hipError_t e = hipErrorInvalidValue;
-      switch ((int)gp.runs[r].pivot.size()) {
-      case 0: e = gates_adjoint_launch_rank<T, 0>(lam, phi, tiles, runs + r, gates, ws, groups, st); break;
-      case 1: e = gates_adjoint_launch_rank<T, 1>(lam, phi, tiles, runs + r, gates, ws, groups, st); break;
-      case 2: e = gates_adjoint_launch_rank<T, 2>(lam, phi, tiles, runs + r, gates, ws, groups, st); break;
-      case 3:
-        if constexpr (sizeof(T) == 8) e = gates_adjoint_launch_rank<T, 3>(lam, phi, tiles, runs + r, gates, ws, groups, st);
-        break;
-      }
+      const hipError_t e = state_with_rank<T, ARTN_GATES_ADJOINT_MAX_RANK>((int)gp.runs[r].pivot.size(), [&](auto rank) {
+        return gates_adjoint_launch_rank<T, decltype(rank)::value>(lam, phi, tiles, runs + r, gates, ws, groups, st);
+      });
       if (e != hipSuccess) return e;
     }
   }
@@ -372,13 +322,13 @@ int artn_gates_adjoint_pack(const ArtnMarginalDesc *d, const int32_t *k, const i
   GatesAdjointPlan ap;
   if (int rc = gates_adjoint_plan(d, k, dims, mat, measure_mat, measure_flag, n_gates, max_rank, ap)) return rc;
   if (!table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_gates_adjoint_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint_pack needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_gates_adjoint_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_gates_adjoint_pack")) return rc;
   const GatesPlan &gp = ap.gp;
-  ArtnGatesHeader *h = (ArtnGatesHeader *)table;
-  ArtnGatesRun *runs = (ArtnGatesRun *)(h + 1);
-  ArtnGatesAdjointGate *gates = (ArtnGatesAdjointGate *)(runs + gp.runs.size());
-  gates_fill_runs(gp, h, runs);
+  ArtnGatesRun *runs;
+  ArtnGatesAdjointGate *gates;
+  state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
+  gates_fill_runs(gp, (ArtnGatesHeader *)table, runs);
   for (int64_t g = 0; g < n_gates; ++g) {
     ArtnGatesAdjointGate rec = {};
     rec.g = gates_fill_gate(gp, g, mat);
@@ -400,13 +350,12 @@ int artn_gates_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const in
   GatesAdjointPlan ap;
   if (int rc = gates_adjoint_plan(d, k, dims, nullptr, nullptr, nullptr, n_gates, max_rank, ap)) return rc; // (matrices and flags are in the table)
   if (!lam || !phi || !table || !workspace || !out) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_gates_adjoint_query reports");
+  if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_gates_adjoint_query")) return rc;
   if (workspace_bytes < ap.info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_gates_adjoint_query reports");
   if ((((uintptr_t)lam | (uintptr_t)phi | (uintptr_t)workspace) & 15) != 0)
     return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint needs 16-byte aligned arrays and workspace");
   if ((((uintptr_t)table | (uintptr_t)out) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint needs an 8-byte aligned table and output");
-  const uintptr_t bytes = (uintptr_t)ap.gp.n * (d->dtype == ARTN_C64 ? 8 : 16), pl = (uintptr_t)lam, pp = (uintptr_t)phi;
-  if (pl < pp + bytes && pp < pl + bytes) return fail(ARTN_E_INVALID, "artn_gates_adjoint: lam overlaps phi");
+  if (int rc = state_disjoint(lam, phi, (uintptr_t)ap.gp.n * (d->dtype == ARTN_C64 ? 8 : 16), "artn_gates_adjoint")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) HIP_TRY(gates_adjoint_launch(ap.gp, (float2 *)lam, (float2 *)phi, table, (double *)workspace, out, st));
   else HIP_TRY(gates_adjoint_launch(ap.gp, (double2 *)lam, (double2 *)phi, table, (double *)workspace, out, st));

@@ -34,46 +34,6 @@
 __device__ __forceinline__ bool gates_adjoint_flagged(const ArtnGatesAdjointGate &g) { return (g.measure & 1) != 0; }
 __device__ __forceinline__ int gates_adjoint_nd(const ArtnGatesAdjointGate &g) { return (g.measure & 2) ? 1 : 1 << (int)g.g.k; }
 
-// gates_add with the coefficients of the measure matrix `mm` (not LANE) or the thread's rows of it in cf (LANE)
-template <typename S, bool LANE, int D>
-__device__ __forceinline__ void gates_adjoint_add(const double (&mm)[4][4][2], const GatesForm &f, int ru_slot, const double (&cf)[2][4][2],
-                                                  const S (&yr)[4], const S (&yi)[4], double (&re)[4], double (&im)[4]) {
-  if (D >= f.nd) return; // (uniform)
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int ru = ru_slot | ((e & f.e0) ? 1 : 0) | ((e & f.e1) ? 2 : 0); // (uniform)
-    double cr, ci;
-    if constexpr (LANE) {
-      const bool h = (ru & f.hbit) != 0;
-      cr = h ? cf[1][D][0] : cf[0][D][0], ci = h ? cf[1][D][1] : cf[0][D][1];
-    } else {
-      cr = mm[ru][ru ^ D][0], ci = mm[ru][ru ^ D][1];
-    }
-    gates_term(cr, ci, yr[e], yi[e], re[e], im[e]);
-  }
-}
-
-// gates_partner for the measure: the partner piece of phi under D, in the order of the own piece
-template <typename T, bool LANE, int D, typename C, typename S>
-__device__ __forceinline__ void gates_adjoint_partner(const double (&mm)[4][4][2], const GatesForm &f, const C *stage, int s, int tid,
-                                                      int ru_slot, const double (&cf)[2][4][2], const S (&xr)[4], const S (&xi)[4],
-                                                      double (&re)[4], double (&im)[4]) {
-  constexpr int Q = (int)sizeof(T) / 4;
-  if (D >= f.nd) return; // (uniform)
-  const int M = ((D & 1) ? f.m0 : 0) ^ ((D & 2) ? f.m1 : 0), P = ((D & 1) ? f.p0 : 0) ^ ((D & 2) ? f.p1 : 0);
-  const int E = ((D & 1) ? f.e0 : 0) ^ ((D & 2) ? f.e1 : 0);
-  S yr[4], yi[4];
-  if (M | P) {
-    pauli_unpack4(pauli_piece_ld(&stage[(s ^ M) * Q * ARTN_BORN_THREADS + (tid ^ P)], ARTN_BORN_THREADS), yr, yi);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) yr[e] = xr[e], yi[e] = xi[e];
-  }
-  if (E & 1) pauli_swap(yr[0], yr[1]), pauli_swap(yi[0], yi[1]), pauli_swap(yr[2], yr[3]), pauli_swap(yi[2], yi[3]);
-  if (E & 2) pauli_swap(yr[0], yr[2]), pauli_swap(yi[0], yi[2]), pauli_swap(yr[1], yr[3]), pauli_swap(yi[1], yi[3]);
-  gates_adjoint_add<S, LANE, D>(mm, f, ru_slot, cf, yr, yi, re, im);
-}
-
 // (tr, ti) += sum over the four elements of slot s of conj(lam) * (M phi): M phi in float64 as gates_slot forms it, not rounded
 template <typename T, bool LANE, typename C, typename S>
 __device__ __forceinline__ void gates_adjoint_measure(const double (&mm)[4][4][2], const GatesForm &f, const C *stage_phi, int s, int tid,
@@ -81,10 +41,10 @@ __device__ __forceinline__ void gates_adjoint_measure(const double (&mm)[4][4][2
                                                       const S (&li)[4], double &tr, double &ti) {
   const int ru_slot = ((s & f.m0) ? 1 : 0) | ((s & f.m1) ? 2 : 0); // (uniform)
   double re[4] = {-0.0, -0.0, -0.0, -0.0}, im[4] = {-0.0, -0.0, -0.0, -0.0};
-  gates_adjoint_partner<T, LANE, 3>(mm, f, stage_phi, s, tid, ru_slot, cf, pr, pi, re, im);
-  gates_adjoint_partner<T, LANE, 2>(mm, f, stage_phi, s, tid, ru_slot, cf, pr, pi, re, im);
-  gates_adjoint_partner<T, LANE, 1>(mm, f, stage_phi, s, tid, ru_slot, cf, pr, pi, re, im);
-  gates_adjoint_add<S, LANE, 0>(mm, f, ru_slot, cf, pr, pi, re, im);
+  gates_partner<T, LANE, 3>(mm, f, stage_phi, s, tid, ru_slot, cf, pr, pi, re, im);
+  gates_partner<T, LANE, 2>(mm, f, stage_phi, s, tid, ru_slot, cf, pr, pi, re, im);
+  gates_partner<T, LANE, 1>(mm, f, stage_phi, s, tid, ru_slot, cf, pr, pi, re, im);
+  gates_add<S, LANE, 0>(mm, f, ru_slot, cf, pr, pi, re, im);
   double qr[4], qi[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -94,27 +54,6 @@ __device__ __forceinline__ void gates_adjoint_measure(const double (&mm)[4][4][2
   }
   tr += (qr[0] + qr[1]) + (qr[2] + qr[3]);
   ti += (qi[0] + qi[1]) + (qi[2] + qi[3]);
-}
-
-// the masks of a gate record, as artn_k_gates reads them
-__device__ __forceinline__ GatesForm gates_adjoint_form(const ArtnGatesGate &g) {
-  GatesForm f;
-  f.nd = (g.flags & ARTN_GATE_DIAGONAL) ? 1 : 1 << (int)g.k;
-  f.m0 = (int)g.slot[0], f.m1 = (int)g.slot[1];
-  f.p0 = (int)g.lo[0] >> 2, f.p1 = (int)g.lo[1] >> 2, f.e0 = (int)g.lo[0] & 3, f.e1 = (int)g.lo[1] & 3;
-  f.hbit = ((int)g.k == 2 ? 3 : 1) & ~((f.p0 ? 1 : 0) | (f.p1 ? 2 : 0));
-  return f;
-}
-
-// the thread's rows of a matrix for both values of the row bit that is not a piece bit (artn_k_gates: LANE)
-__device__ __forceinline__ void gates_adjoint_rows(const double (&m)[4][4][2], const GatesForm &f, int tid, double (&cf)[2][4][2]) {
-  const int rl = ((tid & f.p0) ? 1 : 0) | ((tid & f.p1) ? 2 : 0);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int r = rl | (h ? f.hbit : 0);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) cf[h][d][0] = m[r][r ^ d][0], cf[h][d][1] = m[r][r ^ d][1];
-  }
 }
 
 // ws: [n_gates][ws_groups][ARTN_PAULI_ADJOINT_WAVES][2] float64
@@ -144,12 +83,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates_adjoint(T *lam
   }
   for (long q = blockIdx.x; q < n_blocks; q += gridDim.x) {
     const bool first = q == (long)blockIdx.x;
-    uint64_t rep = (uint64_t)q;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int p = (int)run->pivot[j] - ARTN_PAULI_TILE_BITS;
-      rep = ((rep >> p) << (p + 1)) | (rep & (((uint64_t)1 << p) - 1));
-    }
+    const uint64_t rep = block_rep<R>(run, q);
     S pr[NS][4], pi[NS][4], lr[NS][4], li[NS][4];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -160,7 +94,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates_adjoint(T *lam
     for (int k = 0; k < n_gates; ++k) {
       const ArtnGatesAdjointGate &rec = gp[k];
       const ArtnGatesGate &g = rec.g;
-      const GatesForm f = gates_adjoint_form(g);
+      const GatesForm f = gates_form(g);
       const bool flagged = gates_adjoint_flagged(rec); // (uniform)
       const int nd_m = gates_adjoint_nd(rec);
       const bool moves = (f.m0 | f.m1 | f.p0 | f.p1) != 0;                // (uniform)
@@ -182,7 +116,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates_adjoint(T *lam
         double tr = 0.0, ti = 0.0;
         double cm[2][4][2];
         if (lane) {
-          gates_adjoint_rows(rec.mm, fm, tid, cm);
+          gates_rows(rec.mm, fm, tid, cm);
 #pragma unroll
           for (int s = 0; s < NS; ++s) gates_adjoint_measure<T, true>(rec.mm, fm, stage_phi, s, tid, cm, pr[s], pi[s], lr[s], li[s], tr, ti);
         } else {
@@ -193,7 +127,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates_adjoint(T *lam
       }
       double cf[2][4][2];
       if (lane) {
-        gates_adjoint_rows(g.m, f, tid, cf);
+        gates_rows(g.m, f, tid, cf);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           gates_slot<T, true>(g, f, stage_phi, s, tid, cf, pr[s], pi[s]);

@@ -10,7 +10,7 @@
 //                          gate of the run to it and writes it back -- one read and one write of the state per run
 //   artn_k_gates_small<T>  states below 2^10 elements: one workgroup, the whole circuit in one launch
 //
-// A block is that of artn_k_pauli_evolve: thread t owns elements 4t .. 4t+3 (its PIECE) of every slot and keeps them in registers
+// A block is that of artn_block_kernel.h: thread t owns elements 4t .. 4t+3 (its PIECE) of every slot and keeps them in registers
 // as T for the whole run.  A target is a SLOT bit (high: one bit m of the slot index), a PIECE bit (memory bits 2-9: one bit p of
 // t) or a REGISTER bit (memory bits 0-1: one bit e of the element number); the partner of (slot s, piece t, element e) under d is
 // (s ^ M(d), t ^ P(d), e ^ E(d)), each the XOR of the masks of the targets d flips.
@@ -57,10 +57,33 @@ struct GatesForm {
   int nd, m0, m1, p0, p1, e0, e1, hbit;
 };
 
+// The masks of a gate record, and below the thread's rows of a matrix: what artn_k_gates_adjoint calls.  artn_k_gates has both
+// written out in its body: as calls they change the instructions of every one of its instantiations.
+__device__ __forceinline__ GatesForm gates_form(const ArtnGatesGate &g) {
+  GatesForm f;
+  f.nd = (g.flags & ARTN_GATE_DIAGONAL) ? 1 : 1 << (int)g.k;
+  f.m0 = (int)g.slot[0], f.m1 = (int)g.slot[1];
+  f.p0 = (int)g.lo[0] >> 2, f.p1 = (int)g.lo[1] >> 2, f.e0 = (int)g.lo[0] & 3, f.e1 = (int)g.lo[1] & 3;
+  f.hbit = ((int)g.k == 2 ? 3 : 1) & ~((f.p0 ? 1 : 0) | (f.p1 ? 2 : 0));
+  return f;
+}
+
+// piece targets: the thread's part of the row, and its rows of the matrix `m` for both values of the row bit that may be left
+__device__ __forceinline__ void gates_rows(const double (&m)[4][4][2], const GatesForm &f, int tid, double (&cf)[2][4][2]) {
+  const int rl = ((tid & f.p0) ? 1 : 0) | ((tid & f.p1) ? 2 : 0);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int r = rl | (h ? f.hbit : 0);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) cf[h][d][0] = m[r][r ^ d][0], cf[h][d][1] = m[r][r ^ d][1];
+  }
+}
+
 // Term D of the four elements of one slot: (re, im)[e] += U[r][r ^ D] * (yr, yi)[e], r = ru_slot + the register bits of e + the
-// thread's piece bits.  LANE: cf[h][D] holds the thread's U[r][r ^ D] for the uniform row part 0 (h = 0) and hbit (h = 1).
+// thread's piece bits; U is `m`, the gate's matrix or, in the adjoint kernel, the measure's.  LANE: cf[h][D] holds the thread's
+// U[r][r ^ D] for the uniform row part 0 (h = 0) and hbit (h = 1).
 template <typename S, bool LANE, int D>
-__device__ __forceinline__ void gates_add(const ArtnGatesGate &g, const GatesForm &f, int ru_slot, const double (&cf)[2][4][2],
+__device__ __forceinline__ void gates_add(const double (&m)[4][4][2], const GatesForm &f, int ru_slot, const double (&cf)[2][4][2],
                                           const S (&yr)[4], const S (&yi)[4], double (&re)[4], double (&im)[4]) {
   if (D >= f.nd) return; // (uniform)
 #pragma unroll
@@ -71,7 +94,7 @@ __device__ __forceinline__ void gates_add(const ArtnGatesGate &g, const GatesFor
       const bool h = (ru & f.hbit) != 0;
       cr = h ? cf[1][D][0] : cf[0][D][0], ci = h ? cf[1][D][1] : cf[0][D][1];
     } else {
-      cr = g.m[ru][ru ^ D][0], ci = g.m[ru][ru ^ D][1];
+      cr = m[ru][ru ^ D][0], ci = m[ru][ru ^ D][1];
     }
     gates_term(cr, ci, yr[e], yi[e], re[e], im[e]);
   }
@@ -80,7 +103,7 @@ __device__ __forceinline__ void gates_add(const ArtnGatesGate &g, const GatesFor
 // Term D >= 1 of one slot: the partner piece from the stage (or the own piece when D only flips register bits), its elements
 // brought into the order of the own piece, then gates_add.
 template <typename T, bool LANE, int D, typename C, typename S>
-__device__ __forceinline__ void gates_partner(const ArtnGatesGate &g, const GatesForm &f, const C *stage, int s, int tid, int ru_slot,
+__device__ __forceinline__ void gates_partner(const double (&m)[4][4][2], const GatesForm &f, const C *stage, int s, int tid, int ru_slot,
                                               const double (&cf)[2][4][2], const S (&xr)[4], const S (&xi)[4], double (&re)[4],
                                               double (&im)[4]) {
   constexpr int Q = (int)sizeof(T) / 4;
@@ -94,9 +117,8 @@ __device__ __forceinline__ void gates_partner(const ArtnGatesGate &g, const Gate
 #pragma unroll
     for (int e = 0; e < 4; ++e) yr[e] = xr[e], yi[e] = xi[e];
   }
-  if (E & 1) pauli_swap(yr[0], yr[1]), pauli_swap(yi[0], yi[1]), pauli_swap(yr[2], yr[3]), pauli_swap(yi[2], yi[3]);
-  if (E & 2) pauli_swap(yr[0], yr[2]), pauli_swap(yi[0], yi[2]), pauli_swap(yr[1], yr[3]), pauli_swap(yi[1], yi[3]);
-  gates_add<S, LANE, D>(g, f, ru_slot, cf, yr, yi, re, im);
+  block_swap4(E, yr, yi);
+  gates_add<S, LANE, D>(m, f, ru_slot, cf, yr, yi, re, im);
 }
 
 // One slot of a block under one gate: the terms d = 3 .. 1 from the partners, d = 0 from the own elements, one rounding.
@@ -105,10 +127,10 @@ __device__ __forceinline__ void gates_slot(const ArtnGatesGate &g, const GatesFo
                                            const double (&cf)[2][4][2], S (&xr)[4], S (&xi)[4]) {
   const int ru_slot = ((s & f.m0) ? 1 : 0) | ((s & f.m1) ? 2 : 0); // (uniform)
   double re[4] = {-0.0, -0.0, -0.0, -0.0}, im[4] = {-0.0, -0.0, -0.0, -0.0};
-  gates_partner<T, LANE, 3>(g, f, stage, s, tid, ru_slot, cf, xr, xi, re, im);
-  gates_partner<T, LANE, 2>(g, f, stage, s, tid, ru_slot, cf, xr, xi, re, im);
-  gates_partner<T, LANE, 1>(g, f, stage, s, tid, ru_slot, cf, xr, xi, re, im);
-  gates_add<S, LANE, 0>(g, f, ru_slot, cf, xr, xi, re, im);
+  gates_partner<T, LANE, 3>(g.m, f, stage, s, tid, ru_slot, cf, xr, xi, re, im);
+  gates_partner<T, LANE, 2>(g.m, f, stage, s, tid, ru_slot, cf, xr, xi, re, im);
+  gates_partner<T, LANE, 1>(g.m, f, stage, s, tid, ru_slot, cf, xr, xi, re, im);
+  gates_add<S, LANE, 0>(g.m, f, ru_slot, cf, xr, xi, re, im);
 #pragma unroll
   for (int e = 0; e < 4; ++e) xr[e] = (S)re[e], xi[e] = (S)im[e];
 }
@@ -136,12 +158,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates(T *a, long n_b
     for (int s = 0; s < (1 << j); ++s) span[s | (1 << j)] = span[s] ^ b;
   }
   for (long q = blockIdx.x; q < n_blocks; q += gridDim.x) {
-    uint64_t rep = (uint64_t)q;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int p = (int)run->pivot[j] - ARTN_PAULI_TILE_BITS;
-      rep = ((rep >> p) << (p + 1)) | (rep & (((uint64_t)1 << p) - 1));
-    }
+    const uint64_t rep = block_rep<R>(run, q);
     S xr[NS][4], xi[NS][4];
 #pragma unroll
     for (int s = 0; s < NS; ++s)
@@ -205,13 +222,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates_small(T *a, lo
     const long f0 = (long)g.lo[0], f1 = (long)g.lo[1];
     if (nd > 1) { // (uniform)
       __syncthreads();
-#pragma unroll
-      for (int u = 0; u < PER; ++u) {
-        const long i = tid + u * ARTN_BORN_THREADS;
-        T v;
-        v.x = xr[u], v.y = xi[u];
-        if (i < n) img[i] = v;
-      }
+      block_small_st(img, n, tid, xr, xi);
       __syncthreads();
     }
 #pragma unroll
@@ -234,13 +245,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_gates_small(T *a, lo
       xr[u] = (S)re, xi[u] = (S)im;
     }
   }
-#pragma unroll
-  for (int u = 0; u < PER; ++u) {
-    const long i = tid + u * ARTN_BORN_THREADS;
-    T v;
-    v.x = xr[u], v.y = xi[u];
-    if (i < n) a[i] = v;
-  }
+  block_small_st(a, n, tid, xr, xi);
 }
 
 #endif // ARTN_GATES_KERNEL_H

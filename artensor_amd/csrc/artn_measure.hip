@@ -7,37 +7,18 @@
 #include <vector>
 
 #include "artn_host.h"
+#include "artn_state_host.h"
 #include "artn_measure_kernel.h"
 
 static_assert(sizeof(ArtnMeasureRecord) == ARTN_MEASURE_RECORD_BYTES, "int64 outcome, then probability, total and scale");
 
-// The layout checks of artn_pauli_query (dense: sorted by stride, every stride is the product of the extents below it), then the
-// measured dimensions -- those with keep[] != 0, in the descriptor's order -- as memory bits.
+// The layout checks of artn_pauli_query (artn_state_host.h), then the measured dimensions -- those with keep[] != 0, in the
+// descriptor's order -- as memory bits; what is wrong with them is reported before what the layout does not support.
 static int measure_plan(const ArtnMarginalDesc *d, ArtnMeasureInfo *info, ArtnMeasureArgs *args) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (d->dtype != ARTN_C64 && d->dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "measurement takes complex64 or complex128");
-  if (d->n_dims < 0) return fail(ARTN_E_INVALID, "bad number of dimensions");
-  if (d->n_dims > ARTN_MAX_LABELS) return fail(ARTN_E_UNSUPPORTED, "measurement takes at most 96 dimensions");
-  std::vector<int> order;
-  bool pow2 = true;
-  for (int i = 0; i < d->n_dims; ++i) {
-    if (d->extent[i] < 1) return fail(ARTN_E_INVALID, "extent below 1");
-    if (d->extent[i] == 1) continue; // (carries no index)
-    if (d->stride[i] < 1) return fail(ARTN_E_INVALID, "the tensor is not dense: stride below 1");
-    if (d->extent[i] & (d->extent[i] - 1)) pow2 = false;
-    order.push_back(i);
-  }
-  std::sort(order.begin(), order.end(), [&](int x, int y) { return d->stride[x] < d->stride[y]; });
-  int64_t n = 1;
-  bool too_big = false;
-  for (int i : order) {
-    if (d->stride[i] != n) return fail(ARTN_E_INVALID, "the tensor is not dense: its strides overlap or leave gaps");
-    if (d->extent[i] > ((int64_t)1 << 40) / n) {
-      too_big = true;
-      break;
-    }
-    n *= d->extent[i];
-  }
+  if (int rc = state_desc(d, "measurement takes", ARTN_MAX_LABELS, false)) return rc;
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  const int64_t n = l.n;
   ArtnMeasureInfo out = {};
   ArtnMeasureArgs a = {};
   for (int j = 0; j < ARTN_MEASURE_MAX_DIMS; ++j) out.mem_bit[j] = -1;
@@ -54,8 +35,7 @@ static int measure_plan(const ArtnMarginalDesc *d, ArtnMeasureInfo *info, ArtnMe
     ++k;
   }
   if (k < 1) return fail(ARTN_E_INVALID, "at least one dimension is measured");
-  if (!pow2) return fail(ARTN_E_UNSUPPORTED, "measurement takes power-of-two extents");
-  if (too_big) return fail(ARTN_E_UNSUPPORTED, "measurement takes at most 2^40 elements");
+  if (int rc = state_bits_only(l, "measurement takes")) return rc;
   const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16;
   a.k = k, a.vec_shift = d->dtype == ARTN_C64 ? 1 : 0;
   for (int j = 0; j < k; ++j) a.mask |= (uint64_t)1 << a.bit[j];
@@ -113,7 +93,7 @@ int artn_measure_collapse(const ArtnMarginalDesc *d, void *a, const void *record
   ArtnMeasureArgs p;
   if (int rc = measure_plan(d, &mi, &p)) return rc;
   if (!a || !record) return fail(ARTN_E_INVALID, "null pointer");
-  if (((uintptr_t)a & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_measure_collapse needs a 16-byte aligned array");
+  if (int rc = state_array_aligned(a, "artn_measure_collapse")) return rc;
   if (((uintptr_t)record & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_measure_collapse needs an 8-byte aligned record");
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64)

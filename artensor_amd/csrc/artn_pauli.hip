@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "artn_host.h"
+#include "artn_state_host.h"
 #include "artn_pauli_kernel.h"
 #include "artn_pauli_apply_kernel.h"
 #include "artn_pauli_evolve_kernel.h"
@@ -23,39 +24,17 @@ struct PauliPlan {
   ArtnPauliInfo info = {};
 };
 
-// The layout checks of artn_marginal (dense: sorted by stride, every stride is the product of the extents below it), then every
-// term's memory-bit masks and the groups of equal xmask in the order they first appear.
+// The layout checks of artn_marginal (artn_state_host.h) and power-of-two extents, then every term's memory-bit masks and the
+// groups of equal xmask in the order they first appear.
 static int pauli_plan(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_terms, PauliPlan &pl) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (d->dtype != ARTN_C64 && d->dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "Pauli expectations take complex64 or complex128");
-  if (d->n_dims < 0) return fail(ARTN_E_INVALID, "bad number of dimensions");
-  if (d->n_dims > ARTN_MARG_MAX_DIMS) return fail(ARTN_E_UNSUPPORTED, "Pauli expectations take at most 96 dimensions");
+  if (int rc = state_desc(d, "Pauli expectations take", ARTN_MARG_MAX_DIMS, false)) return rc;
   if (n_terms < 1) return fail(ARTN_E_INVALID, "at least one Pauli string is needed");
   if (!ops) return fail(ARTN_E_INVALID, "null pointer");
   const int nd = d->n_dims;
-  std::vector<int> order;
-  bool pow2 = true;
-  for (int i = 0; i < nd; ++i) {
-    if (d->extent[i] < 1) return fail(ARTN_E_INVALID, "extent below 1");
-    if (d->extent[i] == 1) continue; // (carries no index)
-    if (d->stride[i] < 1) return fail(ARTN_E_INVALID, "the tensor is not dense: stride below 1");
-    if (d->extent[i] & (d->extent[i] - 1)) pow2 = false;
-    order.push_back(i);
-  }
-  std::sort(order.begin(), order.end(), [&](int x, int y) { return d->stride[x] < d->stride[y]; });
-  int64_t n = 1;
-  bool too_big = false;
-  for (int i : order) {
-    if (d->stride[i] != n) return fail(ARTN_E_INVALID, "the tensor is not dense: its strides overlap or leave gaps");
-    if (d->extent[i] > ((int64_t)1 << 40) / n) {
-      too_big = true;
-      break;
-    }
-    n *= d->extent[i];
-  }
-  if (!pow2) return fail(ARTN_E_UNSUPPORTED, "Pauli expectations take power-of-two extents");
-  if (too_big) return fail(ARTN_E_UNSUPPORTED, "Pauli expectations take at most 2^40 elements");
-  pl.n = n;
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  if (int rc = state_bits_only(l, "Pauli expectations take")) return rc;
+  const int64_t n = pl.n = l.n;
   pl.xm.assign(n_terms, 0), pl.zm.assign(n_terms, 0), pl.ny.assign(n_terms, 0), pl.group.assign(n_terms, 0);
   int bit[ARTN_MARG_MAX_DIMS];
   for (int i = 0; i < nd; ++i) bit[i] = d->extent[i] == 2 ? __builtin_ctzll((uint64_t)d->stride[i]) : -1;
@@ -204,8 +183,8 @@ int artn_pauli_apply_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const d
   PauliApplyPlan ap;
   if (int rc = pauli_apply_plan(d, ops, coeff, n_terms, ap)) return rc;
   if (!table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_apply_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_apply_pack needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_pauli_apply_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_pauli_apply_pack")) return rc;
   const PauliPlan &pl = ap.pl;
   ArtnPauliApplyHeader *h = (ArtnPauliApplyHeader *)table;
   ArtnPauliApplyGroup *grp = (ArtnPauliApplyGroup *)(h + 1);
@@ -226,9 +205,9 @@ int artn_pauli_apply(const ArtnMarginalDesc *d, const void *a, void *y, const ui
   PauliApplyPlan ap;
   if (int rc = pauli_apply_plan(d, ops, nullptr, n_terms, ap)) return rc; // (the coefficients are in the table)
   if (!a || !y || !table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ap.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_apply_query reports");
+  if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_pauli_apply_query")) return rc;
   if ((((uintptr_t)a | (uintptr_t)y) & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_apply needs 16-byte aligned arrays");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_apply needs an 8-byte aligned table");
+  if (int rc = state_table_aligned(table, "artn_pauli_apply")) return rc;
   const uintptr_t bytes = (uintptr_t)ap.info.bytes_read, pa = (uintptr_t)a, py = (uintptr_t)y;
   if (pa < py + bytes && py < pa + bytes) return fail(ARTN_E_INVALID, "artn_pauli_apply: y overlaps a (there is no in-place form)");
   const int ng = ap.info.n_groups;
@@ -261,7 +240,7 @@ int artn_pauli_expect(const ArtnMarginalDesc *d, const void *a, const uint8_t *o
   if (int rc = pauli_plan(d, ops, n_terms, pl)) return rc;
   if (!a || !out || !ws) return fail(ARTN_E_INVALID, "null pointer");
   if (ws_bytes < pl.info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_pauli_query reports");
-  if (((uintptr_t)a & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_expect needs a 16-byte aligned array");
+  if (int rc = state_array_aligned(a, "artn_pauli_expect")) return rc;
   if ((((uintptr_t)out | (uintptr_t)ws) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_expect needs 8-byte aligned output and workspace");
   hipStream_t st = (hipStream_t)stream;
   const bool pair_form = pl.n >= ((int64_t)1 << ARTN_PAULI_TILE_BITS);
@@ -323,15 +302,9 @@ static void pauli_evolve_span_add(std::vector<uint64_t> &basis, std::vector<int>
 static int pauli_evolve_plan(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_steps, int32_t max_rank, PauliEvolvePlan &ep) {
   if (int rc = pauli_plan(d, ops, n_steps, ep.pl)) return rc;
   const PauliPlan &pl = ep.pl;
-  const int lib_max = d->dtype == ARTN_C64 ? ARTN_PAULI_EVOLVE_MAX_RANK : ARTN_PAULI_EVOLVE_MAX_RANK - 1;
-  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
-  if (max_rank > lib_max)
-    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the maximum " + std::to_string(lib_max) + " of this dtype");
+  if (int rc = state_max_rank(d->dtype, max_rank, ARTN_PAULI_EVOLVE_MAX_RANK, false, max_rank)) return rc;
   if (n_steps > INT32_MAX) return fail(ARTN_E_UNSUPPORTED, "too many steps in one circuit");
-  if (max_rank < 0) max_rank = lib_max - 1; // 64 KiB of LDS per workgroup
-  int tile_bits = 0;
-  while (((int64_t)1 << (ARTN_PAULI_TILE_BITS + tile_bits + 1)) <= pl.n) ++tile_bits;
-  const int cap = std::min<int>(max_rank, tile_bits);
+  const int cap = state_rank_cap(pl.n, ARTN_PAULI_TILE_BITS, max_rank);
   const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
   ep.run_of.assign(n_steps, 0), ep.slot_mask.assign(n_steps, 0);
   PauliEvolveRunPlan cur;
@@ -387,8 +360,9 @@ static hipError_t pauli_evolve_launch_rank(T *a, long tiles, const ArtnPauliEvol
 
 template <typename T>
 static hipError_t pauli_evolve_launch(const PauliEvolvePlan &ep, T *a, const void *table, hipStream_t st) {
-  const ArtnPauliEvolveRun *runs = (const ArtnPauliEvolveRun *)((const ArtnPauliEvolveHeader *)table + 1);
-  const ArtnPauliEvolveStep *stp = (const ArtnPauliEvolveStep *)(runs + ep.runs.size());
+  const ArtnPauliEvolveRun *runs;
+  const ArtnPauliEvolveStep *stp;
+  state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
   const int64_t n = ep.pl.n;
   if (n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
     hipLaunchKernelGGL(artn_k_pauli_evolve_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, a, (long)n, stp, (int)ep.pl.xm.size());
@@ -396,16 +370,9 @@ static hipError_t pauli_evolve_launch(const PauliEvolvePlan &ep, T *a, const voi
   }
   const long tiles = (long)(n >> ARTN_PAULI_TILE_BITS);
   for (size_t r = 0; r < ep.runs.size(); ++r) {
-    hipError_t e = hipErrorInvalidValue;
-    switch ((int)ep.runs[r].basis.size()) {
-    case 0: e = pauli_evolve_launch_rank<T, 0>(a, tiles, runs + r, stp, st); break;
-    case 1: e = pauli_evolve_launch_rank<T, 1>(a, tiles, runs + r, stp, st); break;
-    case 2: e = pauli_evolve_launch_rank<T, 2>(a, tiles, runs + r, stp, st); break;
-    case 3: e = pauli_evolve_launch_rank<T, 3>(a, tiles, runs + r, stp, st); break;
-    case 4:
-      if constexpr (sizeof(T) == 8) e = pauli_evolve_launch_rank<T, 4>(a, tiles, runs + r, stp, st);
-      break;
-    }
+    const hipError_t e = state_with_rank<T, ARTN_PAULI_EVOLVE_MAX_RANK>((int)ep.runs[r].basis.size(), [&](auto rank) {
+      return pauli_evolve_launch_rank<T, decltype(rank)::value>(a, tiles, runs + r, stp, st);
+    });
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -435,10 +402,10 @@ static void pauli_evolve_fill(const PauliEvolvePlan &ep, const double *coeff, vo
   const PauliPlan &pl = ep.pl;
   const int64_t n_steps = (int64_t)pl.xm.size();
   const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
-  ArtnPauliEvolveHeader *h = (ArtnPauliEvolveHeader *)table;
-  ArtnPauliEvolveRun *runs = (ArtnPauliEvolveRun *)(h + 1);
-  ArtnPauliEvolveStep *stp = (ArtnPauliEvolveStep *)(runs + ep.runs.size());
-  *h = ArtnPauliEvolveHeader{(uint64_t)ep.runs.size(), (uint64_t)n_steps, (uint64_t)ep.info.max_rank, 0};
+  ArtnPauliEvolveRun *runs;
+  ArtnPauliEvolveStep *stp;
+  state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
+  *(ArtnPauliEvolveHeader *)table = ArtnPauliEvolveHeader{(uint64_t)ep.runs.size(), (uint64_t)n_steps, (uint64_t)ep.info.max_rank, 0};
   for (size_t r = 0; r < ep.runs.size(); ++r) {
     const PauliEvolveRunPlan &rp = ep.runs[r];
     ArtnPauliEvolveRun rec = {};
@@ -472,8 +439,8 @@ int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const 
   PauliEvolvePlan ep;
   if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
   if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ep.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_evolve_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve_pack needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, ep.info.table_bytes, "artn_pauli_evolve_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_pauli_evolve_pack")) return rc;
   pauli_evolve_fill(ep, coeff, table);
   return ARTN_OK;
 }
@@ -484,9 +451,9 @@ int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, in
   PauliEvolvePlan ep;
   if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc; // (the coefficients are in the table)
   if (!a || !table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < ep.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_evolve_query reports");
-  if (((uintptr_t)a & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve needs a 16-byte aligned array");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_evolve needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, ep.info.table_bytes, "artn_pauli_evolve_query")) return rc;
+  if (int rc = state_array_aligned(a, "artn_pauli_evolve")) return rc;
+  if (int rc = state_table_aligned(table, "artn_pauli_evolve")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) HIP_TRY(pauli_evolve_launch(ep, (float2 *)a, table, st));
   else HIP_TRY(pauli_evolve_launch(ep, (double2 *)a, table, st));
@@ -501,11 +468,8 @@ int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, in
 static int pauli_adjoint_plan(const ArtnMarginalDesc *d, const uint8_t *ops, const uint8_t *measure, int64_t n_steps, int32_t max_rank,
                               PauliEvolvePlan &ep, ArtnPauliAdjointInfo &info) {
   if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  const int lib_max = d->dtype == ARTN_C128 ? ARTN_PAULI_ADJOINT_MAX_RANK - 1 : ARTN_PAULI_ADJOINT_MAX_RANK;
-  if (max_rank < -1) return fail(ARTN_E_INVALID, "max_rank below -1");
-  if (max_rank > lib_max && (d->dtype == ARTN_C64 || d->dtype == ARTN_C128))
-    return fail(ARTN_E_UNSUPPORTED, "max_rank " + std::to_string(max_rank) + " above the two-state maximum " + std::to_string(lib_max) + " of this dtype");
-  if (int rc = pauli_evolve_plan(d, ops, n_steps, std::min<int32_t>(max_rank < 0 ? lib_max - 1 : max_rank, lib_max), ep)) return rc;
+  if (int rc = state_max_rank(d->dtype, max_rank, ARTN_PAULI_ADJOINT_MAX_RANK, true, max_rank)) return rc;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
   int64_t flagged = n_steps;
   if (measure) flagged = std::count_if(measure, measure + n_steps, [](uint8_t f) { return f != 0; });
   const int64_t groups = std::min<int64_t>(std::max<int64_t>(ep.pl.n >> ARTN_PAULI_TILE_BITS, 1), ARTN_PAULI_EVOLVE_MAX_GRID);
@@ -534,8 +498,9 @@ static hipError_t pauli_adjoint_launch_rank(T *lam, T *phi, long tiles, const Ar
 
 template <typename T>
 static hipError_t pauli_adjoint_launch(const PauliEvolvePlan &ep, T *lam, T *phi, const void *table, double *ws, double *out, hipStream_t st) {
-  const ArtnPauliEvolveRun *runs = (const ArtnPauliEvolveRun *)((const ArtnPauliEvolveHeader *)table + 1);
-  const ArtnPauliEvolveStep *stp = (const ArtnPauliEvolveStep *)(runs + ep.runs.size());
+  const ArtnPauliEvolveRun *runs;
+  const ArtnPauliEvolveStep *stp;
+  state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
   const int64_t n = ep.pl.n;
   const int n_steps = (int)ep.pl.xm.size();
   const long tiles = (long)std::max<int64_t>(n >> ARTN_PAULI_TILE_BITS, 1);
@@ -544,15 +509,9 @@ static hipError_t pauli_adjoint_launch(const PauliEvolvePlan &ep, T *lam, T *phi
     hipLaunchKernelGGL(artn_k_pauli_adjoint_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, lam, phi, (long)n, stp, n_steps, ws);
   } else {
     for (size_t r = 0; r < ep.runs.size(); ++r) {
-      hipError_t e = hipErrorInvalidValue;
-      switch ((int)ep.runs[r].basis.size()) {
-      case 0: e = pauli_adjoint_launch_rank<T, 0>(lam, phi, tiles, runs + r, stp, ws, groups, st); break;
-      case 1: e = pauli_adjoint_launch_rank<T, 1>(lam, phi, tiles, runs + r, stp, ws, groups, st); break;
-      case 2: e = pauli_adjoint_launch_rank<T, 2>(lam, phi, tiles, runs + r, stp, ws, groups, st); break;
-      case 3:
-        if constexpr (sizeof(T) == 8) e = pauli_adjoint_launch_rank<T, 3>(lam, phi, tiles, runs + r, stp, ws, groups, st);
-        break;
-      }
+      const hipError_t e = state_with_rank<T, ARTN_PAULI_ADJOINT_MAX_RANK>((int)ep.runs[r].basis.size(), [&](auto rank) {
+        return pauli_adjoint_launch_rank<T, decltype(rank)::value>(lam, phi, tiles, runs + r, stp, ws, groups, st);
+      });
       if (e != hipSuccess) return e;
     }
   }
@@ -580,10 +539,12 @@ int artn_pauli_adjoint_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const
   ArtnPauliAdjointInfo info;
   if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ep, info)) return rc;
   if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_adjoint_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint_pack needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, info.table_bytes, "artn_pauli_adjoint_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_pauli_adjoint_pack")) return rc;
   pauli_evolve_fill(ep, coeff, table);
-  ArtnPauliEvolveStep *stp = (ArtnPauliEvolveStep *)((ArtnPauliEvolveRun *)((ArtnPauliEvolveHeader *)table + 1) + ep.runs.size());
+  ArtnPauliEvolveRun *runs;
+  ArtnPauliEvolveStep *stp;
+  state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
   for (int64_t k = 0; k < n_steps; ++k) { // n_y, the measure flag and the rank of the step's run share a word
     const uint64_t flag = !measure || measure[k] ? 1 : 0, rank = (uint64_t)ep.runs[ep.run_of[k]].basis.size();
     stp[k].n_y |= flag << 8 | rank << 16;
@@ -598,13 +559,12 @@ int artn_pauli_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const ui
   ArtnPauliAdjointInfo info;
   if (int rc = pauli_adjoint_plan(d, ops, nullptr, n_steps, max_rank, ep, info)) return rc; // (coefficients and flags are in the table)
   if (!lam || !phi || !table || !workspace || !out) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_pauli_adjoint_query reports");
+  if (int rc = state_table_fits(table_bytes, info.table_bytes, "artn_pauli_adjoint_query")) return rc;
   if (workspace_bytes < info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_pauli_adjoint_query reports");
   if ((((uintptr_t)lam | (uintptr_t)phi | (uintptr_t)workspace) & 15) != 0)
     return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint needs 16-byte aligned arrays and workspace");
   if ((((uintptr_t)table | (uintptr_t)out) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint needs an 8-byte aligned table and output");
-  const uintptr_t bytes = (uintptr_t)ep.pl.n * (d->dtype == ARTN_C64 ? 8 : 16), pl = (uintptr_t)lam, pp = (uintptr_t)phi;
-  if (pl < pp + bytes && pp < pl + bytes) return fail(ARTN_E_INVALID, "artn_pauli_adjoint: lam overlaps phi");
+  if (int rc = state_disjoint(lam, phi, (uintptr_t)ep.pl.n * (d->dtype == ARTN_C64 ? 8 : 16), "artn_pauli_adjoint")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) HIP_TRY(pauli_adjoint_launch(ep, (float2 *)lam, (float2 *)phi, table, (double *)workspace, out, st));
   else HIP_TRY(pauli_adjoint_launch(ep, (double2 *)lam, (double2 *)phi, table, (double *)workspace, out, st));

@@ -99,12 +99,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_pauli_adjoint(T *lam
   }
   for (long q = blockIdx.x; q < n_blocks; q += gridDim.x) {
     const bool first = q == (long)blockIdx.x;
-    uint64_t rep = (uint64_t)q;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int p = (int)run->pivot[j] - ARTN_PAULI_TILE_BITS;
-      rep = ((rep >> p) << (p + 1)) | (rep & (((uint64_t)1 << p) - 1));
-    }
+    const uint64_t rep = block_rep<R>(run, q);
     S pr[NS][4], pi[NS][4], lr[NS][4], li[NS][4];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {

@@ -8,19 +8,15 @@
 //                                 every step of the run to it and writes it back -- one read and one write of the state per run
 //   artn_k_pauli_evolve_small<T>  states below 2^10 elements: one workgroup, the whole circuit in one launch
 //
-// A block.  Block q -> the representative tile: q with a 0 inserted at every pivot of the run's reduced-echelon basis, ascending;
-// SLOT s is the tile rep ^ XOR of b_j over the bits j of s.  Thread t owns elements 4t .. 4t+3 (its PIECE) of every slot and
-// keeps them in registers as T for the whole run (16-byte global loads and stores, as artn_k_pauli_apply).  The partner of element
-// (slot s, piece t, e) under a step is (s ^ m, t ^ (xm_lo >> 2), e ^ (xm_lo & 3)), m the step's slot mask.
+// A block, its slots and pieces, the stage and its plane layout: artn_block_kernel.h, with the run's reduced-echelon basis as the
+// vectors.  The partner of element (slot s, piece t, e) under a step is (s ^ m, t ^ (xm_lo >> 2), e ^ (xm_lo & 3)), m the step's
+// slot mask.
 //
 // Who updates what.  Every thread computes its OWN elements from its own registers and the partner's value and writes nothing else:
 //   register steps   m = 0 and xm_lo < 4 (diagonal steps, flips in bits 0-1 only): the partner is one of the thread's own four
 //                    elements of the same slot -- no LDS, no barrier;
-//   staged steps     everything else: barrier, every thread stores its pieces of all slots to LDS, barrier, every thread reads
-//                    the partner piece of each slot (slot s ^ m: an address, never an indexed register) and updates its registers.
-// The stage keeps artn_k_pauli_apply's plane layout per slot, Q = sizeof(T) / 4 planes of 256 x 16 bytes: the ds_read_b128 of a
-// plane at piece t ^ mask touches 16 distinct 16-byte slots in each lane group for every mask -- no bank conflict.  Blocks are
-// disjoint orbits, so no two workgroups touch the same element; stream order separates runs.  No atomics.
+//   staged steps     everything else: the partner piece of each slot (slot s ^ m) comes from the stage.
+// Stream order separates runs.  No atomics.
 //
 // Sign of (P a)[i] at element (slot s, thread t, e): parity(tile_s << 10 & zm) (uniform per slot) ^ parity(4t & zm) (per thread)
 // ^ parity(e & zm) (per element), XORed into the sign bits of the partner's components; (-i)^ny is a swap and sign changes of beta.
@@ -34,6 +30,7 @@
 
 #include "artn.h"
 #include "artn_pauli_apply_kernel.h"
+#include "artn_block_kernel.h"
 
 #define ARTN_PAULI_EVOLVE_MAX_GRID ARTN_BORN_MAX_GRID /* workgroups; each takes blocks g, g + G ... */
 
@@ -83,8 +80,7 @@ __device__ __forceinline__ PauliPiece128 pauli_pack4(const double re[4], const d
 template <typename S>
 __device__ __forceinline__ void pauli_evolve_piece(const PauliEvolveCoef &c, int r, uint32_t sg, const uint32_t pe[4], S xr[4],
                                                    S xi[4], S yr[4], S yi[4]) {
-  if (r & 1) pauli_swap(yr[0], yr[1]), pauli_swap(yi[0], yi[1]), pauli_swap(yr[2], yr[3]), pauli_swap(yi[2], yi[3]);
-  if (r & 2) pauli_swap(yr[0], yr[2]), pauli_swap(yi[0], yi[2]), pauli_swap(yr[1], yr[3]), pauli_swap(yi[1], yi[3]);
+  block_swap4(r, yr, yi);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const uint32_t s = sg ^ pe[e];
@@ -115,12 +111,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_pauli_evolve(T *a, l
     for (int s = 0; s < (1 << j); ++s) span[s | (1 << j)] = span[s] ^ b;
   }
   for (long q = blockIdx.x; q < n_blocks; q += gridDim.x) {
-    uint64_t rep = (uint64_t)q;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int p = (int)run->pivot[j] - ARTN_PAULI_TILE_BITS;
-      rep = ((rep >> p) << (p + 1)) | (rep & (((uint64_t)1 << p) - 1));
-    }
+    const uint64_t rep = block_rep<R>(run, q);
     S xr[NS][4], xi[NS][4];
 #pragma unroll
     for (int s = 0; s < NS; ++s)
@@ -178,13 +169,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_pauli_evolve_small(T
     const uint64_t zm = stp[k].zmask;
     const long xm = (long)stp[k].xm_lo; // (the whole mask: n <= 2^9)
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const long i = tid + u * ARTN_BORN_THREADS;
-      T v;
-      v.x = xr[u], v.y = xi[u];
-      if (i < n) img[i] = v;
-    }
+    block_small_st(img, n, tid, xr, xi);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
@@ -195,13 +180,7 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_pauli_evolve_small(T
       pauli_evolve_pair(c, xr[u], xi[u], pauli_evolve_flip(b.x, sg), pauli_evolve_flip(b.y, sg));
     }
   }
-#pragma unroll
-  for (int u = 0; u < PER; ++u) {
-    const long i = tid + u * ARTN_BORN_THREADS;
-    T v;
-    v.x = xr[u], v.y = xi[u];
-    if (i < n) a[i] = v;
-  }
+  block_small_st(a, n, tid, xr, xi);
 }
 
 #endif // ARTN_PAULI_EVOLVE_KERNEL_H

@@ -7,43 +7,25 @@
 #include <vector>
 
 #include "artn_host.h"
+#include "artn_state_host.h"
 #include "artn_rdm_kernel.h"
 
-static int rdm_ceil_log2(int64_t n) {
-  int b = 0;
-  while (b < 62 && ((int64_t)1 << b) < n) ++b;
-  return b;
-}
-
-// The layout checks of artn_marginal (dense: sorted by stride, every stride is the product of the extents below it), then the form.
+// The layout checks of artn_marginal (artn_state_host.h), then the form.
 static int rdm_plan(const ArtnMarginalDesc *d, ArtnRdmInfo *info, ArtnRdmStream *sp, ArtnRdmGeneric *gp, int64_t *n_sum) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (d->dtype != ARTN_C64 && d->dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "reduced density matrices take complex64 or complex128");
-  if (d->n_dims < 0 || d->n_dims > ARTN_RDM_MAX_DIMS) return fail(ARTN_E_INVALID, "bad number of dimensions");
-  std::vector<int> order;
-  bool pow2 = true;
-  for (int i = 0; i < d->n_dims; ++i) {
-    if (d->extent[i] < 1) return fail(ARTN_E_INVALID, "extent below 1");
-    if (d->extent[i] == 1) continue; // (carries no index)
-    if (d->stride[i] < 1) return fail(ARTN_E_INVALID, "the tensor is not dense: stride below 1");
-    if (d->extent[i] & (d->extent[i] - 1)) pow2 = false;
-    order.push_back(i);
-  }
-  std::sort(order.begin(), order.end(), [&](int x, int y) { return d->stride[x] < d->stride[y]; });
-  int64_t n = 1;
-  for (int i : order) {
-    if (d->stride[i] != n) return fail(ARTN_E_INVALID, "the tensor is not dense: its strides overlap or leave gaps");
-    if (d->extent[i] > ((int64_t)1 << 40) / n) return fail(ARTN_E_INVALID, "element count out of range");
-    n *= d->extent[i];
-  }
+  if (int rc = state_desc(d, "reduced density matrices take", ARTN_RDM_MAX_DIMS, true)) return rc;
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  if (l.too_big) return fail(ARTN_E_INVALID, "element count out of range");
+  const int64_t n = l.n;
+  const bool pow2 = l.pow2;
   int64_t D = 1;
-  for (int i : order)
+  for (int i : l.order)
     if (d->keep[i]) D *= d->extent[i];
   if (D > ((int64_t)1 << ARTN_RDM_MAX_DIM_BITS))
     return fail(ARTN_E_UNSUPPORTED, "reduced density matrices keep at most 1024 states; this one keeps " + std::to_string(D));
   ArtnRdmInfo out = {};
   out.dim = D;
-  const int nbits = rdm_ceil_log2(n), k = rdm_ceil_log2(D);
+  const int nbits = state_ceil_log2(n), k = state_ceil_log2(D);
   const int rowb = std::max(k, 4), trb = std::min(rowb, 6), cb = ARTN_RDM_PANEL_BITS - trb;
   if (pow2 && nbits >= ARTN_RDM_MIN_BITS && D >= 2 && nbits - rowb >= cb) {
     ArtnRdmStream s = {};
@@ -53,7 +35,7 @@ static int rdm_plan(const ArtnMarginalDesc *d, ArtnRdmInfo *info, ArtnRdmStream 
     int ob = 0;
     for (int i = d->n_dims - 1; i >= 0; --i) {
       if (d->extent[i] == 1 || !d->keep[i]) continue;
-      const int e = rdm_ceil_log2(d->extent[i]), s0 = rdm_ceil_log2(d->stride[i]);
+      const int e = state_ceil_log2(d->extent[i]), s0 = state_ceil_log2(d->stride[i]);
       for (int b = 0; b < e; ++b) {
         kmask |= (uint64_t)1 << (s0 + b);
         out_of_mem_bit[s0 + b] = ob++;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "artn_host.h"
+#include "artn_state_host.h"
 #include "artn_wgate_kernel.h"
 
 struct WgatePlan {
@@ -20,34 +21,13 @@ struct WgatePlan {
 // The layout checks of artn_gates_query, then the target bits and the tile (include/artn.h: PLAN).  `mat` may be null
 // (artn_wgate_apply: the matrix is in the table); the flag "diagonal" is then not set.
 static int wgate_plan(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const double *mat, WgatePlan &wp) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (d->dtype != ARTN_C64 && d->dtype != ARTN_C128) return fail(ARTN_E_UNSUPPORTED, "wide gates take complex64 or complex128");
-  if (d->n_dims < 0) return fail(ARTN_E_INVALID, "bad number of dimensions");
-  if (d->n_dims > ARTN_MARG_MAX_DIMS) return fail(ARTN_E_UNSUPPORTED, "wide gates take at most 96 dimensions");
+  if (int rc = state_desc(d, "wide gates take", ARTN_MARG_MAX_DIMS, false)) return rc;
   if (!dims) return fail(ARTN_E_INVALID, "null pointer");
   const int nd = d->n_dims;
-  std::vector<int> order;
-  bool pow2 = true;
-  for (int i = 0; i < nd; ++i) {
-    if (d->extent[i] < 1) return fail(ARTN_E_INVALID, "extent below 1");
-    if (d->extent[i] == 1) continue; // (carries no index)
-    if (d->stride[i] < 1) return fail(ARTN_E_INVALID, "the tensor is not dense: stride below 1");
-    if (d->extent[i] & (d->extent[i] - 1)) pow2 = false;
-    order.push_back(i);
-  }
-  std::sort(order.begin(), order.end(), [&](int x, int y) { return d->stride[x] < d->stride[y]; });
-  int64_t n = 1;
-  bool too_big = false;
-  for (int i : order) {
-    if (d->stride[i] != n) return fail(ARTN_E_INVALID, "the tensor is not dense: its strides overlap or leave gaps");
-    if (d->extent[i] > ((int64_t)1 << 40) / n) {
-      too_big = true;
-      break;
-    }
-    n *= d->extent[i];
-  }
-  if (!pow2) return fail(ARTN_E_UNSUPPORTED, "wide gates take power-of-two extents");
-  if (too_big) return fail(ARTN_E_UNSUPPORTED, "wide gates take at most 2^40 elements");
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  if (int rc = state_bits_only(l, "wide gates take")) return rc;
+  const int64_t n = l.n;
   if (k < 1 || k > ARTN_WGATE_MAX_K)
     return fail(ARTN_E_UNSUPPORTED, "wide gates act on one to five dimensions, not " + std::to_string(k));
   const int n_bits = __builtin_ctzll((uint64_t)n);
@@ -65,14 +45,8 @@ static int wgate_plan(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims,
       if (dims[i] == dim) return fail(ARTN_E_INVALID, "the dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
     wp.target.push_back(__builtin_ctzll((uint64_t)d->stride[dim]));
   }
-  bool diagonal = mat != nullptr;
-  if (mat) {
-    const int rows = 1 << k;
-    for (int e = 0; e < 2 * rows * rows; ++e) {
-      if (!std::isfinite(mat[e])) return fail(ARTN_E_INVALID, "a matrix entry is not finite");
-      if (mat[e] != 0.0 && (e / 2) / rows != (e / 2) % rows) diagonal = false;
-    }
-  }
+  bool diagonal = false;
+  if (mat && !state_matrix_scan(mat, 1 << k, diagonal)) return fail(ARTN_E_INVALID, "a matrix entry is not finite");
   const int tb_max = d->dtype == ARTN_C64 ? ARTN_WGATE_TILE_BITS_C64 : ARTN_WGATE_TILE_BITS_C128;
   wp.tb = std::min(tb_max, n_bits);
   wp.tile = wp.target;
@@ -123,8 +97,8 @@ int artn_wgate_pack(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, c
   WgatePlan wp;
   if (int rc = wgate_plan(d, k, dims, mat, wp)) return rc;
   if (!table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < wp.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_wgate_query reports");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_wgate_pack needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, wp.info.table_bytes, "artn_wgate_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_wgate_pack")) return rc;
   ArtnWgateTable t = {};
   const int rows = 1 << k, gb = wp.tb - k;
   t.k = (uint64_t)k, t.tile_bits = (uint64_t)wp.tb, t.n_tiles = (uint64_t)wp.info.n_tiles, t.segment = (uint64_t)wp.info.segment;
@@ -165,9 +139,9 @@ int artn_wgate_apply(const ArtnMarginalDesc *d, void *a, int32_t k, const int32_
   WgatePlan wp;
   if (int rc = wgate_plan(d, k, dims, nullptr, wp)) return rc;
   if (!a || !table) return fail(ARTN_E_INVALID, "null pointer");
-  if (table_bytes < wp.info.table_bytes) return fail(ARTN_E_INVALID, "table smaller than artn_wgate_query reports");
-  if (((uintptr_t)a & 15) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_wgate_apply needs a 16-byte aligned array");
-  if (((uintptr_t)table & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_wgate_apply needs an 8-byte aligned table");
+  if (int rc = state_table_fits(table_bytes, wp.info.table_bytes, "artn_wgate_query")) return rc;
+  if (int rc = state_array_aligned(a, "artn_wgate_apply")) return rc;
+  if (int rc = state_table_aligned(table, "artn_wgate_apply")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == ARTN_C64) wgate_launch(wp, (float2 *)a, table, st);
   else wgate_launch(wp, (double2 *)a, table, st);

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two source trees of this project, kernel by kernel.
 
-    python3 tools/compare_device_code.py OLD_TREE NEW_TREE [--dev] [--jobs N] [--out report.md]
+    python3 tools/compare_device_code.py OLD_TREE NEW_TREE [--dev] [--jobs N] [--objects a,b,c] [--out report.md]
 
 For each tree the compile commands of the library's objects are taken from `make -n -B all` (with --dev: DEV=1), every
 object is compiled again with `--offload-device-only -S`, and the assembly is split per kernel symbol into: instruction
 text, the .amdhsa_kernel descriptor block and the kernel's metadata record (.vgpr_count, .sgpr_count, LDS, scratch, ...).
 The only thing normalised is the per-compilation `__hip_cuid_<hash>` symbol.  Objects are matched by name, so a kernel that
-moves to another object shows up as missing in one and new in the other.
+moves to another object shows up as missing in one and new in the other.  --objects restricts both trees to the named
+objects (for example born,rdm,pauli,gates,wgate,measure).
 Exit status 0 when every object emits the same kernel symbols in both trees and every kernel is identical (--dev: equal
 names and register counts).
 """
@@ -75,9 +76,14 @@ def split_kernels(asm):
     return {s: (text[s], desc[s], meta.get(s, "")) for s in desc}
 
 
-def tree_kernels(tree, dev, jobs):
+def tree_kernels(tree, dev, jobs, objects):
     """{(object, symbol): parts}: template instantiations that several objects emit (weak symbols) count once per object"""
     cmds = compile_commands(tree, dev)
+    if objects:
+        missing = sorted(set(objects) - set(cmds))
+        if missing:
+            sys.exit("%s builds no object named %s" % (tree, ", ".join(missing)))
+        cmds = {u: cmds[u] for u in objects}
     kernels = {}
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(jobs) as ex:
         for unit, asm in ex.map(lambda kv: emit_asm(tree, kv[0], kv[1], tmp), sorted(cmds.items())):
@@ -96,10 +102,11 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--dev", action="store_true")
     ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--objects", type=lambda v: [u for u in v.split(",") if u], help="compare only these objects, e.g. born,rdm")
     ap.add_argument("--out")
     a = ap.parse_args()
-    ko, uo = tree_kernels(a.old, a.dev, a.jobs)
-    kn, un = tree_kernels(a.new, a.dev, a.jobs)
+    ko, uo = tree_kernels(a.old, a.dev, a.jobs, a.objects)
+    kn, un = tree_kernels(a.new, a.dev, a.jobs, a.objects)
     rep = ["## %s build" % ("Development (`make dev`)" if a.dev else "Product (`make`)"), ""]
     rep.append("| object | kernels, old tree | kernels, new tree |")
     rep.append("|---|---|---|")
