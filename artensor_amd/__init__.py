@@ -112,6 +112,16 @@ from .wide_gates import (  # noqa: F401
     fuse_gates,
     wide_gate_info,
 )
+from . import controlled  # noqa: F401
+from .controlled import (  # noqa: F401
+    ControlledGate,
+    apply_controlled_gate_,
+    controlled_gate_info,
+    mcphase_,
+    mcx_,
+    mcz_,
+    when,
+)
 from . import krylov  # noqa: F401
 from .krylov import (  # noqa: F401
     KrylovResult,

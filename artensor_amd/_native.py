@@ -213,6 +213,29 @@ WGATE_MAX_K = 5
 WGATE_TILE_BITS = {ARTN_C64: 12, ARTN_C128: 11}
 WGATE_TABLE_HEADER_BYTES = 480
 
+
+class ArtnCgateInfo(ctypes.Structure):
+    _fields_ = [
+        ("t", ctypes.c_int32),
+        ("c", ctypes.c_int32),
+        ("c_high", ctypes.c_int32),
+        ("c_low", ctypes.c_int32),
+        ("tile_bits", ctypes.c_int32),
+        ("diagonal", ctypes.c_int32),
+        ("n_selected", ctypes.c_int64),
+        ("n_tiles", ctypes.c_int64),
+        ("segment", ctypes.c_int64),
+        ("lds_bytes", ctypes.c_int64),
+        ("table_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
+CGATE_LINE_BITS = {ARTN_C64: 4, ARTN_C128: 3}
+CGATE_MAX_HOLES = 64
+CGATE_TABLE_HEADER_BYTES = 1000
+
 KRYLOV_BATCH = 8
 KRYLOV_MAX_VECS = 64
 
@@ -368,6 +391,15 @@ _EXPORTS = {
                                        ctypes.c_void_p, ctypes.c_int64]),
     "artn_wgate_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: one dense gate under any number of controls and a device-resident condition (has("artn_cgate_apply"))
+    "artn_cgate_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ArtnCgateInfo),
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_cgate_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "artn_cgate_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     # additive to ABI 9 as well: the vector algebra of Krylov drivers (has("artn_krylov_combine"))
     "artn_krylov_query": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ArtnKrylovInfo)]),
     "artn_krylov_dots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,

@@ -867,6 +867,93 @@ int artn_measure_choose(const double *q, int64_t D, const double *uniform, int64
                         void *stream);
 int artn_measure_collapse(const ArtnMarginalDesc *d, void *a, const void *record, int32_t reset, void *stream);
 
+/*
+ * ONE dense gate on one to five TARGET qubits under any number of CONTROL qubits, optionally under a classical condition read
+ * from device memory, in place, in one launch (additive to ABI 9: has("artn_cgate_apply")).  targets[0 .. t-1] (t = 1..5) and
+ * controls[0 .. c-1] (c >= 0; NULL where c == 0) are distinct dimensions of extent 2, disjoint from each other; every dimension
+ * that is no target may be a control.  control_values[j] is 0 or 1, the digit control j must have (NULL: all 1).  mat is the
+ * 2^t x 2^t matrix of artn_wgate_query on the targets, the FIRST listed target the most significant digit; any finite matrix.
+ *
+ * CONTRACT.  An element is SELECTED when its control digits equal control_values.  A selected element becomes what the
+ * ARITHMETIC contract of artn_wgate_apply gives for mat on the targets (terms d = 2^t - 1 .. 0, accumulators from -0.0, float64
+ * fma, products of exactly-zero coefficient components left out, one rounding per component).  An UNSELECTED element keeps its
+ * bits -- the sign of a zero, NaN payloads, denormals, infinities: no arithmetic touches it; one that shares a tile with selected
+ * elements may be loaded and stored back raw, the elements of every other tile are neither read nor written.  So c = 0 and no
+ * condition is artn_wgate_apply bit for bit; for c + t <= 5 on finite data the result is artn_wgate_apply of the matrix
+ * |v><v| (x) U + (1 - |v><v|) (x) I bit for bit; the identity changes nothing; a signed permutation is exact; the controls count
+ * as a set of (dimension, value) pairs.  No atomics: results are bit-identical from run to run.
+ * CONDITION.  cond is NULL or points at an int64 o in DEVICE memory (8-byte aligned): the gate is applied iff o >= 0 and
+ * (o & cond_mask) == cond_value.  Otherwise every workgroup returns before its first access to the state, which stays untouched
+ * bit for bit.  The first 8 bytes of the record of artn_measure_choose are such an int64; its outcome -1 never triggers a gate.
+ *
+ * PLAN.  A dimension of stride 2^b is memory bit b; LB = 4 (complex64) or 3 (complex128) is the number of index bits of a
+ * 128-byte line.  A control below bit LB is a LOW control: skipping it would save no memory traffic, so it stays an ordinary
+ * index bit of the tile.  Every other control is a HIGH control and is removed from the index space: the launch walks only the
+ * n >> c_high elements whose high control bits are as wanted.  The TILE BITS are the t target bits and the lowest memory bits
+ * that are neither targets nor high controls, TB = ARTN_WGATE_TILE_BITS_C64 / _C128 in all or the whole selected sub-state
+ * (log2 n - c_high bits) where that is smaller -- one workgroup then; tile-local bit j is the j-th tile bit in ascending order.
+ * Bits 0 .. LB-1 always lie in the tile, so it is made of contiguous SEGMENTS of `segment` = 2^s elements, at least 128 bytes
+ * where the state has them (s = the number of leading tile bits j that are memory bit j).  The HOLES are the tile bits at or
+ * above s and the high controls; tile q starts at the element whose index is q << s with a 0 inserted at every hole bit,
+ * ascending, OR high_want.  LDS layout, swizzle, phases and block_mask are those of artn_wgate_apply with k = t; a low control
+ * is one of the group bits, and an item whose group index g has (g & group_mask) != group_want is not computed: the LDS image
+ * keeps what was loaded and the store phase writes it back raw.
+ *
+ * TABLE (what artn_cgate_pack writes and the kernel reads; 8-byte little-endian fields): ArtnCgateTable, 1000 bytes, then the
+ * matrix as float64 (Re, Im), row-major, 16 * 4^t bytes.  table_bytes = 1000 + 16 * 4^t.
+ *
+ * ARTN_E_UNSUPPORTED: t outside 1..5, the layout and dtype refusals of artn_wgate_query, a table that is not 8-byte aligned,
+ * an array that is not 16-byte aligned, a cond that is not 8-byte aligned.  ARTN_E_INVALID: c < 0, t above the number of memory
+ * bits, a dimension out of range, repeated, both target and control, or of extent other than 2, a control value other than 0 / 1,
+ * a matrix entry that is not finite, a null pointer, a table smaller than the query's.
+ */
+#define ARTN_CGATE_MAX_HOLES 64
+typedef struct ArtnCgateTable {
+  uint64_t t, tile_bits, n_tiles, segment;
+  uint64_t flags;        /* ARTN_GATE_DIAGONAL                                                                        */
+  uint64_t group_bits;   /* tile_bits - t                                                                              */
+  uint64_t segment_bits; /* log2(segment)                                                                              */
+  uint64_t block_mask;   /* as ArtnWgateTable's                                                                        */
+  uint64_t n_holes;      /* entries of hole_bit                                                                        */
+  uint64_t high_want;    /* OR of 1 << b over the high controls b whose wanted value is 1                              */
+  uint64_t high_mask;    /* OR of 1 << b over the high controls                                                        */
+  uint64_t group_mask;   /* OR of 1 << r over the low controls, r the control's bit of the group index                 */
+  uint64_t group_want;   /* the same over the low controls whose wanted value is 1                                     */
+  uint64_t target_bit[ARTN_WGATE_MAX_K]; /* the memory bits of the targets in the order listed                        */
+  uint64_t target_pos[ARTN_WGATE_MAX_K]; /* their tile-local positions, same order                                    */
+  uint64_t swizzle[ARTN_WGATE_MAX_K];    /* per ROW bit i (the i-th target from the last listed one)                  */
+  uint64_t mem_col[16];                  /* per tile-local bit j: 1 << its memory bit (0 beyond tile_bits)            */
+  uint64_t lds_col[16];                  /* per tile-local bit j: what it contributes (XOR) to the LDS index          */
+  uint64_t hole_bit[ARTN_CGATE_MAX_HOLES]; /* ascending: tile bits at or above segment_bits, and the high controls    */
+  uint64_t reserved;
+} ArtnCgateTable;
+typedef struct ArtnCgateInfo {
+  int32_t t, c;
+  int32_t c_high, c_low;
+  int32_t tile_bits;     /* TB, or log2 of the selected sub-state when that is smaller   */
+  int32_t diagonal;      /* 1: every off-diagonal entry is exactly 0                      */
+  int64_t n_selected;    /* n >> c: the elements the gate acts on                         */
+  int64_t n_tiles;       /* n_tiles << tile_bits = n >> c_high                            */
+  int64_t segment;       /* elements of a contiguous segment of a tile                    */
+  int64_t lds_bytes;
+  int64_t table_bytes;
+  int64_t bytes_read;    /* (n >> c_high) elements                                        */
+  int64_t bytes_written;
+} ArtnCgateInfo;
+/* Host-only: validates and plans.  target_bits (t entries, the order listed), control_bits (c entries, the order listed) and
+ * tile_bits (info->tile_bits entries, ascending; room for 12) may be NULL. */
+int artn_cgate_query(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
+                     const int32_t *control_values, const double *mat, ArtnCgateInfo *info, int32_t *target_bits,
+                     int32_t *control_bits, int32_t *tile_bits);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_cgate_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
+                    const int32_t *control_values, const double *mat, void *table, int64_t table_bytes);
+/* The gate on `a`, in place: ONE launch on `stream`.  `table` is DEVICE memory holding what artn_cgate_pack wrote for the same
+ * descriptor, targets, controls and control values.  No allocation, copy or synchronisation.  ARTN_E_NODEVICE without a device. */
+int artn_cgate_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
+                     const int32_t *control_values, const void *table, int64_t table_bytes, const void *cond, int64_t cond_mask,
+                     int64_t cond_value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
