@@ -140,6 +140,20 @@ from .measure import (  # noqa: F401
     postselect_,
     reset_,
 )
+from . import channel  # noqa: F401
+from .channel import (  # noqa: F401
+    Channel,
+    ChannelOp,
+    amplitude_damping,
+    bit_flip,
+    channel_,
+    channel_info,
+    channel_step_,
+    depolarizing,
+    pauli_channel,
+    phase_damping,
+    phase_flip,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

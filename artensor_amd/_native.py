@@ -273,6 +273,32 @@ class ArtnMeasureInfo(ctypes.Structure):
     ]
 
 
+CHANNEL_MAX_OPS = 256
+CHANNEL_FIXED, CHANNEL_DIAGONAL, CHANNEL_DENSE = 0, 1, 2
+CHANNEL_FORMS = ("FIXED", "DIAGONAL", "DENSE")
+CHANNEL_OP_DIAGONAL, CHANNEL_OP_IDENTITY = 1, 2
+CHANNEL_TABLE_HEADER_BYTES = 512
+
+
+class ArtnChannelInfo(ctypes.Structure):
+    _fields_ = [
+        ("t", ctypes.c_int32),
+        ("m", ctypes.c_int32),
+        ("form", ctypes.c_int32),
+        ("tile_bits", ctypes.c_int32),
+        ("launches", ctypes.c_int32 * 3),
+        ("reduction", ctypes.c_int32 * 3),
+        ("n_tiles", ctypes.c_int64),
+        ("segment", ctypes.c_int64),
+        ("lds_bytes", ctypes.c_int64),
+        ("weight_doubles", ctypes.c_int64),
+        ("table_bytes", ctypes.c_int64),
+        ("record_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -412,6 +438,18 @@ _EXPORTS = {
                                            ctypes.c_void_p, ctypes.c_void_p]),
     "artn_measure_collapse": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                              ctypes.c_void_p]),
+    # additive to ABI 9 as well: noise channels drawn and applied on the device (has("artn_channel_apply"))
+    "artn_channel_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ArtnChannelInfo), ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "artn_channel_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "artn_channel_choose": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p]),
+    "artn_channel_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_void_p]),
 }
 
 

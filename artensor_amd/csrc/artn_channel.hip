@@ -1,0 +1,236 @@
+// artn_channel.hip -- host half of the noise-channel entry points artn_channel_* of include/artn.h (kernels: artn_channel_kernel.h).
+//
+// A translation unit of its own (build/obj/channel.o).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "artn_host.h"
+#include "artn_state_host.h"
+#include "artn_channel_kernel.h"
+
+static_assert(sizeof(ArtnChannelTable) == 512 && sizeof(ArtnChannelOp) == 16, "the table's header and operator records");
+static_assert(sizeof(ArtnChannelRecord) == ARTN_MEASURE_RECORD_BYTES, "int64 outcome, then probability, total and scale");
+
+struct ChannelPlan {
+  int t = 0, m = 0, form = 0, n_bits = 0, tb = 0, seg_bits = 0;
+  std::vector<int> target; // memory bits in the order listed
+  std::vector<int> tile;   // tile bits, ascending
+  ArtnChannelInfo info = {};
+};
+
+static int64_t channel_weight_doubles(int form, int t) {
+  return form == ARTN_CHANNEL_FIXED ? 1 : form == ARTN_CHANNEL_DIAGONAL ? (int64_t)1 << t : (int64_t)2 << (2 * t);
+}
+
+// t, m and form alone: what artn_channel_choose can check (it sees no descriptor)
+static int channel_counts(int32_t t, int32_t m, int32_t form) {
+  if (t < 1 || t > ARTN_WGATE_MAX_K)
+    return fail(ARTN_E_UNSUPPORTED, "channels act on one to five dimensions, not " + std::to_string(t));
+  if (m < 1 || m > ARTN_CHANNEL_MAX_OPS)
+    return fail(ARTN_E_INVALID, "a channel has 1 to " + std::to_string(ARTN_CHANNEL_MAX_OPS) + " operators, not " + std::to_string(m));
+  if (form != ARTN_CHANNEL_FIXED && form != ARTN_CHANNEL_DIAGONAL && form != ARTN_CHANNEL_DENSE)
+    return fail(ARTN_E_INVALID, "unknown weight form " + std::to_string(form));
+  return ARTN_OK;
+}
+
+static int64_t channel_table_bytes(int t, int m, int form) {
+  return (int64_t)sizeof(ArtnChannelTable) + (int64_t)m * ((int64_t)sizeof(ArtnChannelOp) + 8 * channel_weight_doubles(form, t) +
+                                                           ((int64_t)16 << (2 * t)));
+}
+static int64_t channel_record_bytes(int t) { return ARTN_MEASURE_RECORD_BYTES + ((int64_t)16 << (2 * t)); }
+
+// The layout checks and the tile of artn_wgate_query (include/artn.h: PLAN), then m and the form.  `mats` may be null: nothing
+// is scanned then.
+static int channel_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t m, int32_t form, const double *mats,
+                        ChannelPlan &cp) {
+  if (int rc = state_desc(d, "channels take", ARTN_MARG_MAX_DIMS, false)) return rc;
+  if (!dims) return fail(ARTN_E_INVALID, "null pointer");
+  const int nd = d->n_dims;
+  StateLayout l;
+  if (int rc = state_layout(d, l)) return rc;
+  if (int rc = state_bits_only(l, "channels take")) return rc;
+  const int64_t n = l.n;
+  if (t < 1 || t > ARTN_WGATE_MAX_K)
+    return fail(ARTN_E_UNSUPPORTED, "channels act on one to five dimensions, not " + std::to_string(t));
+  const int n_bits = __builtin_ctzll((uint64_t)n);
+  if (t > n_bits)
+    return fail(ARTN_E_INVALID, "a channel on " + std::to_string(t) + " dimensions needs a state of at least 2^" + std::to_string(t) +
+                                    " elements; this one has " + std::to_string((long long)n));
+  cp.t = t, cp.m = m, cp.form = form, cp.n_bits = n_bits;
+  for (int j = 0; j < t; ++j) {
+    const int32_t dim = dims[j];
+    if (dim < 0 || dim >= nd) return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " out of range");
+    if (d->extent[dim] != 2)
+      return fail(ARTN_E_INVALID, "channels act on dimensions of extent 2; dimension " + std::to_string(dim) + " has extent " +
+                                      std::to_string(d->extent[dim]));
+    for (int i = 0; i < j; ++i)
+      if (dims[i] == dim) return fail(ARTN_E_INVALID, "the dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
+    cp.target.push_back(__builtin_ctzll((uint64_t)d->stride[dim]));
+  }
+  if (int rc = channel_counts(t, m, form)) return rc;
+  if (mats)
+    for (int j = 0; j < m; ++j) {
+      bool diagonal = false;
+      if (!state_matrix_scan(mats + ((size_t)j << (2 * t + 1)), 1 << t, diagonal))
+        return fail(ARTN_E_INVALID, "an entry of operator " + std::to_string(j) + " is not finite");
+    }
+  const int tb_max = d->dtype == ARTN_C64 ? ARTN_WGATE_TILE_BITS_C64 : ARTN_WGATE_TILE_BITS_C128;
+  cp.tb = std::min(tb_max, n_bits);
+  cp.tile = cp.target;
+  for (int b = 0; (int)cp.tile.size() < cp.tb; ++b)
+    if (std::find(cp.target.begin(), cp.target.end(), b) == cp.target.end()) cp.tile.push_back(b);
+  std::sort(cp.tile.begin(), cp.tile.end());
+  cp.seg_bits = 0;
+  while (cp.seg_bits < cp.tb && cp.tile[cp.seg_bits] == cp.seg_bits) ++cp.seg_bits;
+  const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16;
+  ArtnChannelInfo &ci = cp.info;
+  ci.t = t, ci.m = m, ci.form = form, ci.tile_bits = cp.tb;
+  for (int f = 0; f < 3; ++f) ci.launches[f] = 2, ci.reduction[f] = f;
+  ci.n_tiles = n >> cp.tb, ci.segment = (int64_t)1 << cp.seg_bits, ci.lds_bytes = elem << cp.tb;
+  ci.weight_doubles = channel_weight_doubles(form, t);
+  ci.table_bytes = channel_table_bytes(t, m, form), ci.record_bytes = channel_record_bytes(t);
+  ci.bytes_read = ci.bytes_written = n * elem;
+  return ARTN_OK;
+}
+
+template <typename T>
+static void channel_launch(const ChannelPlan &cp, T *a, const void *table, const void *record, hipStream_t st) {
+  const ArtnChannelTable *tab = (const ArtnChannelTable *)table;
+  const ArtnChannelRecord *rec = (const ArtnChannelRecord *)record;
+  const dim3 grid((unsigned)std::min<int64_t>(cp.info.n_tiles, ARTN_WGATE_MAX_GRID)), block(ARTN_BORN_THREADS);
+  const size_t lds = (size_t)cp.info.lds_bytes;
+  const int m = cp.m;
+  switch (cp.t) {
+  case 1: hipLaunchKernelGGL((artn_k_channel<T, 1>), grid, block, lds, st, a, tab, rec, m); break;
+  case 2: hipLaunchKernelGGL((artn_k_channel<T, 2>), grid, block, lds, st, a, tab, rec, m); break;
+  case 3: hipLaunchKernelGGL((artn_k_channel<T, 3>), grid, block, lds, st, a, tab, rec, m); break;
+  case 4: hipLaunchKernelGGL((artn_k_channel<T, 4>), grid, block, lds, st, a, tab, rec, m); break;
+  case 5: hipLaunchKernelGGL((artn_k_channel<T, 5>), grid, block, lds, st, a, tab, rec, m); break;
+  }
+}
+
+static int channel_record_fits(int64_t record_bytes, int t) {
+  if (record_bytes < channel_record_bytes(t)) return fail(ARTN_E_INVALID, "record smaller than artn_channel_query reports");
+  return ARTN_OK;
+}
+
+extern "C" {
+
+int artn_channel_query(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t m, int32_t form, const double *mats,
+                       ArtnChannelInfo *info, int32_t *target_bits, int32_t *tile_bits) {
+  if (!info) return fail(ARTN_E_INVALID, "null info");
+  ChannelPlan cp;
+  if (int rc = channel_plan(d, t, dims, m, form, mats, cp)) return rc;
+  *info = cp.info;
+  if (target_bits) std::copy(cp.target.begin(), cp.target.end(), target_bits);
+  if (tile_bits) std::copy(cp.tile.begin(), cp.tile.end(), tile_bits);
+  return ARTN_OK;
+}
+
+int artn_channel_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t m, int32_t form, const double *mats,
+                      const double *weights, void *table, int64_t table_bytes) {
+  if (!mats || !weights) return fail(ARTN_E_INVALID, "null pointer");
+  ChannelPlan cp;
+  if (int rc = channel_plan(d, t, dims, m, form, mats, cp)) return rc;
+  const int64_t wd = cp.info.weight_doubles;
+  for (int64_t e = 0; e < wd * m; ++e)
+    if (!std::isfinite(weights[e])) return fail(ARTN_E_INVALID, "a weight of operator " + std::to_string(e / wd) + " is not finite");
+  if (!table) return fail(ARTN_E_INVALID, "null pointer");
+  if (int rc = state_table_fits(table_bytes, cp.info.table_bytes, "artn_channel_query")) return rc;
+  if (int rc = state_table_aligned(table, "artn_channel_pack")) return rc;
+  ArtnChannelTable ct = {};
+  ArtnWgateTable &g = ct.gate;
+  const int rows = 1 << t, gb = cp.tb - t;
+  g.k = (uint64_t)t, g.tile_bits = (uint64_t)cp.tb, g.n_tiles = (uint64_t)cp.info.n_tiles, g.segment = (uint64_t)cp.info.segment;
+  g.group_bits = (uint64_t)gb, g.n_high = (uint64_t)(cp.tb - cp.seg_bits);
+  for (int j = cp.seg_bits; j < cp.tb; ++j) g.high_bit[j - cp.seg_bits] = (uint64_t)cp.tile[j];
+  // the swizzle of artn_wgate_pack: the window is the lowest P = min(6, gb) tile-local bits; its non-targets are group bits
+  // 0 .. P-j-1 and LDS index bits of the same number, its j targets get the LDS index bits P-j .. P-1
+  const int window = std::min(6, gb);
+  int low_targets = 0;
+  for (int p = 0; p < window; ++p)
+    if (std::find(cp.target.begin(), cp.target.end(), cp.tile[p]) != cp.target.end()) ++low_targets;
+  int rank = 0, seen = 0; // non-targets / window targets below the position
+  for (int p = 0; p < cp.tb; ++p) {
+    g.mem_col[p] = (uint64_t)1 << cp.tile[p];
+    const auto at = std::find(cp.target.begin(), cp.target.end(), cp.tile[p]);
+    if (at == cp.target.end()) {
+      g.lds_col[p] = (uint64_t)1 << rank++;
+      continue;
+    }
+    const int listed = (int)(at - cp.target.begin()), row_bit = t - 1 - listed; // the LAST listed target is row bit 0
+    g.target_bit[listed] = (uint64_t)cp.tile[p], g.target_pos[listed] = (uint64_t)p;
+    if (p < window) g.swizzle[row_bit] = (uint64_t)1 << (window - low_targets + seen++);
+    g.lds_col[p] = ((uint64_t)1 << (gb + row_bit)) ^ g.swizzle[row_bit];
+  }
+  ct.m = (uint64_t)m, ct.form = (uint64_t)form, ct.weight_doubles = (uint64_t)wd;
+  // per operator: the block mask of artn_wgate_pack, "diagonal" and "exactly the identity"
+  const int r = std::min(rows, ARTN_WGATE_ROWS), nb = rows / r;
+  ArtnChannelOp *ops = (ArtnChannelOp *)((ArtnChannelTable *)table + 1);
+  bool all_diagonal = true;
+  for (int j = 0; j < m; ++j) {
+    const double *mat = mats + ((size_t)j << (2 * t + 1));
+    ArtnChannelOp op = {};
+    bool diagonal = true, identity = true;
+    for (int row = 0; row < rows; ++row)
+      for (int col = 0; col < rows; ++col) {
+        const double re = mat[2 * (row * rows + col)], im = mat[2 * (row * rows + col) + 1];
+        if (re != 0.0 || im != 0.0) {
+          op.block_mask |= (uint64_t)1 << ((row / r) * nb + col / r);
+          if (row != col) diagonal = false;
+        }
+        if (re != (row == col ? 1.0 : 0.0) || im != 0.0) identity = false;
+      }
+    op.flags = (diagonal ? ARTN_CHANNEL_OP_DIAGONAL : 0) | (identity ? ARTN_CHANNEL_OP_IDENTITY : 0);
+    ops[j] = op;
+    g.block_mask |= op.block_mask;
+    all_diagonal = all_diagonal && diagonal;
+  }
+  g.flags = all_diagonal ? ARTN_GATE_DIAGONAL : 0;
+  *(ArtnChannelTable *)table = ct;
+  double *w = (double *)(ops + m);
+  std::copy(weights, weights + wd * m, w);
+  std::copy(mats, mats + ((size_t)m << (2 * t + 1)), w + wd * m);
+  return ARTN_OK;
+}
+
+int artn_channel_choose(const void *table, int64_t table_bytes, int32_t t, int32_t m, int32_t form, const double *input,
+                        const double *uniform, int32_t renormalize, void *record, int64_t record_bytes, void *stream) {
+  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
+  if (int rc = channel_counts(t, m, form)) return rc;
+  if (!table || !uniform || !record || (form != ARTN_CHANNEL_FIXED && !input)) return fail(ARTN_E_INVALID, "null pointer");
+  if (int rc = state_table_fits(table_bytes, channel_table_bytes(t, m, form), "artn_channel_query")) return rc;
+  if (int rc = channel_record_fits(record_bytes, t)) return rc;
+  if (int rc = state_table_aligned(table, "artn_channel_choose")) return rc;
+  if ((((uintptr_t)input | (uintptr_t)uniform | (uintptr_t)record) & 7) != 0)
+    return fail(ARTN_E_UNSUPPORTED, "artn_channel_choose needs 8-byte aligned arrays");
+  hipLaunchKernelGGL(artn_k_channel_choose, dim3(1), dim3(ARTN_CHANNEL_THREADS), 0, (hipStream_t)stream,
+                     (const ArtnChannelTable *)table, (int)t, (int)m, (int)form, input, uniform, (int)renormalize,
+                     (ArtnChannelRecord *)record);
+  HIP_TRY(hipGetLastError());
+  return ARTN_OK;
+}
+
+int artn_channel_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_t *dims, int32_t m, const void *table,
+                       int64_t table_bytes, const void *record, int64_t record_bytes, void *stream) {
+  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
+  ChannelPlan cp;
+  if (int rc = channel_plan(d, t, dims, m, ARTN_CHANNEL_FIXED, nullptr, cp)) return rc;
+  if (!a || !table || !record) return fail(ARTN_E_INVALID, "null pointer");
+  // (the smallest table of any form: the kernel reads the header and the operator records only)
+  if (int rc = state_table_fits(table_bytes, cp.info.table_bytes, "artn_channel_query")) return rc;
+  if (int rc = channel_record_fits(record_bytes, t)) return rc;
+  if (int rc = state_array_aligned(a, "artn_channel_apply")) return rc;
+  if (int rc = state_table_aligned(table, "artn_channel_apply")) return rc;
+  if (((uintptr_t)record & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_channel_apply needs an 8-byte aligned record");
+  hipStream_t st = (hipStream_t)stream;
+  if (d->dtype == ARTN_C64) channel_launch(cp, (float2 *)a, table, record, st);
+  else channel_launch(cp, (double2 *)a, table, record, st);
+  HIP_TRY(hipGetLastError());
+  return ARTN_OK;
+}
+
+} // extern "C"

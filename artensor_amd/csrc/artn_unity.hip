@@ -26,3 +26,4 @@
 #include "artn_cgate.hip" // (artn_cgate_kernel.h)
 #include "artn_krylov.hip" // (artn_krylov_kernel.h)
 #include "artn_measure.hip" // (artn_measure_kernel.h)
+#include "artn_channel.hip" // (artn_channel_kernel.h)

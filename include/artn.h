@@ -954,6 +954,96 @@ int artn_cgate_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_
                      const int32_t *control_values, const void *table, int64_t table_bytes, const void *cond, int64_t cond_mask,
                      int64_t cond_value, void *stream);
 
+/*
+ * NOISE CHANNELS for quantum trajectories: one of m operators on t target qubits is drawn ON THE DEVICE and applied in place
+ * (additive to ABI 9: has("artn_channel_apply")).  dims[0 .. t-1] (t = 1..5) are distinct dimensions of extent 2, the FIRST listed
+ * one the most significant digit (the convention of artn_wgate_query, artn_marginal and artn_rdm); mats holds the m (1..256)
+ * operators as float64 [m][2 * 4^t], each a 2^t x 2^t matrix row-major, Re and Im interleaved.  D = 2^t.
+ *
+ * FORM (decided by the caller at pack time) says where the weights w_j of the draw come from:
+ *   ARTN_CHANNEL_FIXED     weights[m]: w_j = weights[j].  mats are the U_j of a mixture sum_j p_j U_j rho U_j^+ as given; no pass over
+ *                          the state is made for the draw, `input` of artn_channel_choose is not read and scale is exactly 1.
+ *   ARTN_CHANNEL_DIAGONAL  weights[m][D]: e_j[d] = sum_r |K_j[r,d]|^2 (every K_j has at most one non-zero per column, so K_j^+ K_j is
+ *                          diagonal).  input = q, the D float64 artn_marginal writes for dims.  w_j = sum_d e_j[d] q[d]: an fma chain
+ *                          from 0.0 over d ascending.  trace = q[0] + q[1] + ... ascending.
+ *   ARTN_CHANNEL_DENSE     weights[m][D][D][2]: E_j = K_j^+ K_j row-major (Re, Im).  input = rho, the [D][D][2] float64 artn_rdm writes
+ *                          for dims.  w_j = sum_{a,b} Re(E_j[a,b] rho[b,a]): an fma chain from 0.0 over a ascending, inside it b
+ *                          ascending, per (a, b) first + Re E Re rho, then - Im E Im rho.  trace = Re rho[0,0] + Re rho[1,1] + ...
+ * A w_j below 0 (rounding residue) or NaN counts as 0.
+ *
+ * artn_channel_choose: ONE workgroup.  Lanes form the w_j, one operator per lane at a time; one lane then applies the choice rule
+ *   of artn_measure_choose to them: total = w_0 + w_1 + ... ascending; j is the smallest index whose inclusive running sum (the
+ *   same additions) exceeds uniform * total, or the last j with w_j > 0 where rounding leaves none; a j with w_j == 0 is never
+ *   chosen.  The RECORD (DEVICE, record_bytes of the query, 8-byte aligned) starts with the 32 bytes of artn_measure_choose's:
+ *       int64 j; float64 probability = w_j / total, total, scale;
+ *   scale = sqrt(trace / w_j), so that sum |a|^2 after the step equals trace; scale = 1 where renormalize == 0 and in the FIXED
+ *   form.  Where total (or, outside the FIXED form, trace) is not finite or not > 0 nothing can be drawn: j = -1, probability 0,
+ *   scale 1.  Behind the 32 bytes lies the CURRENT MATRIX, float64 [2 * 4^t]: every component of operator j times scale, one
+ *   float64 multiply each (all +0.0 where j = -1).
+ * artn_channel_apply: ONE launch, the tile kernel of artn_wgate_apply with the current matrix as its matrix; PLAN, LDS layout and
+ *   ARITHMETIC are artn_wgate_apply's, so the state afterwards is bit for bit what artn_wgate_apply gives for the current matrix.
+ *   The kernel reads j from the record.  Where j < 0 or j >= m, and where operator j is an exact identity matrix (flagged at pack
+ *   time) and scale == 1.0, every workgroup returns before its first access to the state, which stays untouched bit for bit --
+ *   non-finite data included, which artn_wgate_apply of the identity promises for finite data only.  The all-zero 8 x 8 blocks of
+ *   operator j (its block_mask, from the table) are skipped as artn_wgate_apply skips those of its matrix.
+ * Both run on `stream`, take the caller's buffers and do no allocation, copy or synchronisation.  No atomics: results are
+ * bit-identical from run to run.
+ *
+ * TABLE (what artn_channel_pack writes and the kernels read; 8-byte little-endian fields): ArtnChannelTable, 512 bytes -- its
+ * first 480 bytes are an ArtnWgateTable for the same descriptor and dims whose block_mask is the OR and whose flags the AND over
+ * the operators, so with m = 1 it is what artn_wgate_pack writes for that matrix -- then m ArtnChannelOp (16 bytes each), then the
+ * weights (8 * weight_doubles * m bytes), then the m matrices (16 * 4^t bytes each).
+ *
+ * ARTN_E_UNSUPPORTED: t outside 1..5, the layout and dtype refusals of artn_wgate_query in the wording "channels take ...", a
+ * table, record or array that is not aligned (table, record, input, uniform: 8 bytes; the state: 16).  ARTN_E_INVALID: m outside
+ * 1..256, an unknown form, t above the number of memory bits, a dimension out of range, repeated or of extent other than 2, a
+ * matrix entry or weight that is not finite, a null pointer, a table or record smaller than the query's.  ARTN_E_NODEVICE without a
+ * device (query and pack are host-only).
+ */
+#define ARTN_CHANNEL_MAX_OPS 256
+#define ARTN_CHANNEL_FIXED 0
+#define ARTN_CHANNEL_DIAGONAL 1
+#define ARTN_CHANNEL_DENSE 2
+#define ARTN_CHANNEL_OP_DIAGONAL 1 /* ArtnChannelOp.flags: every off-diagonal entry is exactly 0 */
+#define ARTN_CHANNEL_OP_IDENTITY 2 /* ArtnChannelOp.flags: the matrix is exactly the identity    */
+typedef struct ArtnChannelOp {
+  uint64_t block_mask; /* as ArtnWgateTable's, of this operator */
+  uint64_t flags;
+} ArtnChannelOp;
+typedef struct ArtnChannelTable {
+  ArtnWgateTable gate;     /* k = t; block_mask: OR over the operators; flags: AND over the operators         */
+  uint64_t m;              /* operators                                                                        */
+  uint64_t form;           /* ARTN_CHANNEL_FIXED / _DIAGONAL / _DENSE                                         */
+  uint64_t weight_doubles; /* float64 per operator in the weights: 1, D or 2 D^2                               */
+  uint64_t reserved;
+} ArtnChannelTable;
+typedef struct ArtnChannelInfo {
+  int32_t t, m, form;
+  int32_t tile_bits;        /* TB, or log2 of the state when that is smaller                                   */
+  int32_t launches[3];      /* per form: the launches of choose + apply (2); the DIAGONAL form adds those of   */
+  int32_t reduction[3];     /* artn_marginal, the DENSE form those of artn_rdm -- reduction[form]: 0 none, 1 marginal, 2 rdm */
+  int64_t n_tiles, segment, lds_bytes;
+  int64_t weight_doubles;   /* float64 per operator the pack reads from `weights`                             */
+  int64_t table_bytes;      /* 512 + m * (16 + 8 * weight_doubles + 16 * 4^t)                                  */
+  int64_t record_bytes;     /* 32 + 16 * 4^t                                                                   */
+  int64_t bytes_read;       /* nominal, of the pass over the state (none under the early return)              */
+  int64_t bytes_written;
+} ArtnChannelInfo;
+/* Host-only: validates and plans.  mats may be NULL (no matrix is scanned then).  target_bits (t entries, the order listed) and
+ * tile_bits (info->tile_bits entries, ascending; room for 12) may be NULL. */
+int artn_channel_query(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t m, int32_t form, const double *mats,
+                       ArtnChannelInfo *info, int32_t *target_bits, int32_t *tile_bits);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_channel_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t m, int32_t form, const double *mats,
+                      const double *weights, void *table, int64_t table_bytes);
+/* The draw: one launch of one workgroup on `stream`.  `table` is DEVICE memory holding what artn_channel_pack wrote for t, m and
+ * form; `input` (DEVICE; may be NULL in the FIXED form) is q or rho as above; `uniform` is one float64 in [0, 1) in DEVICE memory. */
+int artn_channel_choose(const void *table, int64_t table_bytes, int32_t t, int32_t m, int32_t form, const double *input,
+                        const double *uniform, int32_t renormalize, void *record, int64_t record_bytes, void *stream);
+/* The pass over `a`, in place: one launch on `stream`, reading the record artn_channel_choose wrote. */
+int artn_channel_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_t *dims, int32_t m, const void *table,
+                       int64_t table_bytes, const void *record, int64_t record_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
