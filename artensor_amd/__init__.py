@@ -154,6 +154,17 @@ from .channel import (  # noqa: F401
     phase_damping,
     phase_flip,
 )
+from . import diagonal  # noqa: F401
+from .diagonal import (  # noqa: F401
+    DiagonalOperator,
+    diagonal_evolve_,
+    diagonal_expectation,
+    diagonal_info,
+    diagonal_values,
+    ising_terms,
+    maxcut_terms,
+    qaoa_gradient,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

@@ -299,6 +299,29 @@ class ArtnChannelInfo(ctypes.Structure):
     ]
 
 
+DIAG_MAX_GROUPS, DIAG_MAX_TERMS, DIAG_TILE_BITS = 64, 65536, 10
+DIAG_PHASE, DIAG_MULTIPLY = 0, 1
+DIAG_PAIR_EVOLVE, DIAG_PAIR_TRANSITION = 0, 1
+DIAG_OPS = ("VALUES", "EXPECT", "PHASE", "MULTIPLY", "PAIR")
+DIAG_TABLE_HEADER_BYTES = 64
+
+
+class ArtnDiagInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_terms", ctypes.c_int32),
+        ("n_static", ctypes.c_int32),
+        ("n_dynamic", ctypes.c_int32),
+        ("n_groups", ctypes.c_int32),
+        ("tile_bits", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("n_tiles", ctypes.c_int64),
+        ("table_bytes", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64 * 5),
+        ("bytes_written", ctypes.c_int64 * 5),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -450,6 +473,22 @@ _EXPORTS = {
     "artn_channel_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_void_p]),
+    # additive to ABI 9 as well: diagonal operators -- cost-function phases, moments and pairs in one pass (has("artn_diag_apply"))
+    "artn_diag_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.POINTER(ArtnDiagInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_diag_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_void_p, ctypes.c_int64]),
+    "artn_diag_values": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_diag_expect": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                        ctypes.c_void_p]),
+    "artn_diag_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]),
+    "artn_diag_pair": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 

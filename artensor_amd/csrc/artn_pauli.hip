@@ -37,23 +37,12 @@ static int pauli_plan(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_t
   const int64_t n = pl.n = l.n;
   pl.xm.assign(n_terms, 0), pl.zm.assign(n_terms, 0), pl.ny.assign(n_terms, 0), pl.group.assign(n_terms, 0);
   int bit[ARTN_MARG_MAX_DIMS];
-  for (int i = 0; i < nd; ++i) bit[i] = d->extent[i] == 2 ? __builtin_ctzll((uint64_t)d->stride[i]) : -1;
+  state_dim_bits(d, bit);
   std::unordered_map<uint64_t, int32_t> group_of;
   for (int64_t t = 0; t < n_terms; ++t) {
-    const uint8_t *op = ops + t * nd;
     uint64_t x = 0, z = 0;
     int32_t y = 0;
-    for (int i = 0; i < nd; ++i) {
-      if (op[i] > 3) return fail(ARTN_E_INVALID, "term " + std::to_string(t) + ": operator code " + std::to_string(op[i]) + " (0..3 = I, X, Y, Z)");
-      if (op[i] == 0) continue;
-      if (bit[i] < 0)
-        return fail(ARTN_E_INVALID, "term " + std::to_string(t) + ": X, Y and Z act on dimensions of extent 2; dimension " +
-                                        std::to_string(i) + " has extent " + std::to_string(d->extent[i]));
-      const uint64_t b = (uint64_t)1 << bit[i];
-      if (op[i] != 3) x |= b;
-      if (op[i] != 1) z |= b;
-      if (op[i] == 2) ++y;
-    }
+    if (int rc = state_string_masks(d, bit, ops + t * nd, t, x, z, y)) return rc;
     pl.xm[t] = x, pl.zm[t] = z, pl.ny[t] = y;
     auto it = group_of.find(x);
     if (it == group_of.end()) {

@@ -1,5 +1,5 @@
 // artn_state_host.h -- host plumbing shared by the operations on a dense amplitude array (artn_born.hip, artn_rdm.hip,
-// artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip): the descriptor and layout checks, the max_rank rule and the
+// artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip): the descriptor and layout checks, the max_rank rule and the
 // rank dispatch of the run kernels, the matrix scan, the argument checks of the pack / apply entries and the parts of a packed
 // table.  Codes and texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording
 // (`who`: "gate circuits take", ...) and its own precedence between the errors, so the pieces are separate functions.
@@ -59,6 +59,27 @@ static int state_layout(const ArtnMarginalDesc *d, StateLayout &l) {
 static int state_bits_only(const StateLayout &l, const char *who) {
   if (!l.pow2) return fail(ARTN_E_UNSUPPORTED, std::string(who) + " power-of-two extents");
   if (l.too_big) return fail(ARTN_E_UNSUPPORTED, std::string(who) + " at most 2^40 elements");
+  return ARTN_OK;
+}
+
+// Pauli strings (uint8 codes 0..3 = I, X, Y, Z per dimension): the memory bit of every dimension of extent 2 (-1 elsewhere), and
+// the masks of term t -- x: the bits under X or Y, z: those under Z or Y, y: the number of Y
+static void state_dim_bits(const ArtnMarginalDesc *d, int *bit) {
+  for (int i = 0; i < d->n_dims; ++i) bit[i] = d->extent[i] == 2 ? __builtin_ctzll((uint64_t)d->stride[i]) : -1;
+}
+static int state_string_masks(const ArtnMarginalDesc *d, const int *bit, const uint8_t *op, int64_t t, uint64_t &x, uint64_t &z, int32_t &y) {
+  x = z = 0, y = 0;
+  for (int i = 0; i < d->n_dims; ++i) {
+    if (op[i] > 3) return fail(ARTN_E_INVALID, "term " + std::to_string(t) + ": operator code " + std::to_string(op[i]) + " (0..3 = I, X, Y, Z)");
+    if (op[i] == 0) continue;
+    if (bit[i] < 0)
+      return fail(ARTN_E_INVALID, "term " + std::to_string(t) + ": X, Y and Z act on dimensions of extent 2; dimension " +
+                                      std::to_string(i) + " has extent " + std::to_string(d->extent[i]));
+    const uint64_t b = (uint64_t)1 << bit[i];
+    if (op[i] != 3) x |= b;
+    if (op[i] != 1) z |= b;
+    if (op[i] == 2) ++y;
+  }
   return ARTN_OK;
 }
 

@@ -27,3 +27,4 @@
 #include "artn_krylov.hip" // (artn_krylov_kernel.h)
 #include "artn_measure.hip" // (artn_measure_kernel.h)
 #include "artn_channel.hip" // (artn_channel_kernel.h)
+#include "artn_diag.hip" // (artn_diag_kernel.h)

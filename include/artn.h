@@ -1044,6 +1044,99 @@ int artn_channel_choose(const void *table, int64_t table_bytes, int32_t t, int32
 int artn_channel_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_t *dims, int32_t m, const void *table,
                        int64_t table_bytes, const void *record, int64_t record_bytes, void *stream);
 
+/*
+ * DIAGONAL OPERATORS: a classical cost function f(i) = sum_k c_k (-1)^popcount(i & zmask_k) applied as ONE object, one streaming
+ * pass per operation whatever the number of terms (additive to ABI 9: has("artn_diag_apply")).  Descriptor, `ops` (uint8
+ * [n_terms][n_dims], I and Z only: codes 0 and 3), masks and layout refusals are those of artn_pauli_query in the wording
+ * "diagonal operators take ..."; `coeff` is float64 [n_terms] (real).  Repeated strings are allowed and are not merged.
+ *
+ * PLAN.  The tile is TB = min(10, log2 n) low memory bits; lo_k = zmask_k & (2^TB - 1), hi_k = zmask_k >> TB.  A term with
+ * hi_k == 0 is STATIC; the others are DYNAMIC and form GROUPS of equal lo_k, numbered in the order they first appear (a group
+ * with lo == 0 is a per-tile constant).  More than ARTN_DIAG_MAX_GROUPS groups: ARTN_E_UNSUPPORTED.
+ *
+ * VALUE CONTRACT (float64; every c * (+-1) is exact, so these are plain sequential additions, never fused):
+ *     S[l]    = ((0.0 + s_1) + s_2) + ...   over the static terms in the caller's order, s_k = +-c_k by popcount(l & lo_k)
+ *     w_g(h)  = ((0.0 + s_1) + s_2) + ...   over the terms of group g in the caller's order, s_k = +-c_k by popcount(h & hi_k)
+ *     f(h, l) = ((S[l] + sigma_0 w_0(h)) + sigma_1 w_1(h)) + ...   over the groups in order, sigma_g = +-1 by popcount(l & lo_g)
+ * for the element at memory index (h << TB) | l.  S is computed by artn_diag_pack on the host; every tile computes its w_g(h) on
+ * the device.  f depends on the memory index and the term list alone -- not on the dtype, the grid or the workgroup.
+ *
+ * OPERATIONS (one launch each on `stream`, plus a one-workgroup finish launch where a sum is returned; 256 threads, the grid
+ * min(tiles, 2048) striding over tiles; no atomics, sums in float64 in a fixed order: bit-identical from run to run):
+ *   artn_diag_values   out[i] = f(i), float64, n entries in memory order (DEVICE).
+ *   artn_diag_expect   out[0..2] = sum p, sum p f, sum (p f) f with p = fma(ar, ar, ai * ai) in float64 (as artn_born_overlap),
+ *                      accumulated as fma(p, f, acc) and fma(p f, f, acc).
+ *   artn_diag_apply    ARTN_DIAG_PHASE:    a[i] <- a[i] * exp(-i gamma f(i)): phi = gamma * f (one rounding), float64 sincos,
+ *                                          Re = fma(ar, c, ai * s), Im = fma(ai, c, -(ar * s)), rounded once to the dtype.
+ *                                          gamma == 0 returns without a launch.
+ *                      ARTN_DIAG_MULTIPLY: a[i] <- a[i] * f(i): one float64 product per component, rounded once (gamma unused).
+ *   artn_diag_pair     lam and phi of one descriptor, byte ranges disjoint.  out[0..1] = Re, Im of sum_i conj(lam_i) f(i) phi_i
+ *                      from the values BEFORE the phase: u = conj(lam_i) phi_i (Re = fma(lr, pr, li * pi), Im = fma(lr, pi,
+ *                      -(li * pr))), acc = fma(u, f, acc).  ARTN_DIAG_PAIR_EVOLVE: both states take ARTN_DIAG_PHASE in the same
+ *                      pass (gamma == 0: nothing is written) and are afterwards bit for bit what artn_diag_apply leaves on each
+ *                      alone; ARTN_DIAG_PAIR_TRANSITION: nothing is written.
+ * `ops` and n_terms are those of the pack call (the plan is rebuilt from them; the coefficients are in the table).  The calls take
+ * the caller's table (DEVICE, 8-byte aligned) and workspace (DEVICE, 8-byte aligned, workspace_bytes of the query) and do no
+ * allocation, copy or synchronisation.
+ *
+ * TABLE (what artn_diag_pack writes and the kernels read; 8-byte little-endian fields): ArtnDiagTable (64 bytes), S as 2^TB
+ * float64, n_groups ArtnDiagGroup (32 bytes each, in group order), then n_dynamic ArtnDiagTerm (16 bytes each, group by group,
+ * the caller's order inside a group).  table_bytes = 64 + 8 * 2^TB + 32 * n_groups + 16 * n_dynamic.
+ *
+ * ARTN_E_INVALID: a layout that is not dense, an operator code above 3, X or Y in a term, Z on an extent other than 2, n_terms < 1,
+ * a coefficient or gamma that is not finite, an unknown mode, a null pointer, a table or workspace smaller
+ * than the query's, byte ranges of lam and phi that overlap.  ARTN_E_UNSUPPORTED: another dtype, an extent that is no power of two,
+ * more than 96 dimensions or 2^40 elements, more than ARTN_DIAG_MAX_GROUPS groups or ARTN_DIAG_MAX_TERMS terms, a state that is not 16-byte aligned, a table,
+ * workspace or output that is not 8-byte aligned.  ARTN_E_NODEVICE without a device (query and pack are host-only).
+ */
+#define ARTN_DIAG_MAX_GROUPS 64
+#define ARTN_DIAG_MAX_TERMS 65536
+#define ARTN_DIAG_TILE_BITS 10
+#define ARTN_DIAG_PHASE 0
+#define ARTN_DIAG_MULTIPLY 1
+#define ARTN_DIAG_PAIR_EVOLVE 0
+#define ARTN_DIAG_PAIR_TRANSITION 1
+#define ARTN_DIAG_OP_VALUES 0 /* the indices of ArtnDiagInfo.bytes_read / bytes_written */
+#define ARTN_DIAG_OP_EXPECT 1
+#define ARTN_DIAG_OP_PHASE 2
+#define ARTN_DIAG_OP_MULTIPLY 3
+#define ARTN_DIAG_OP_PAIR 4
+typedef struct ArtnDiagTable {
+  uint64_t n_terms, n_static, n_dynamic, n_groups, tile_bits, n_tiles, reserved[2];
+} ArtnDiagTable;
+typedef struct ArtnDiagGroup {
+  uint64_t lo, first, count, reserved; /* the group's terms are the term records first .. first + count - 1 */
+} ArtnDiagGroup;
+typedef struct ArtnDiagTerm {
+  uint64_t hi;
+  double c;
+} ArtnDiagTerm;
+typedef struct ArtnDiagInfo {
+  int32_t n_terms, n_static, n_dynamic, n_groups;
+  int32_t tile_bits; /* TB */
+  int32_t reserved;
+  int64_t n_tiles;
+  int64_t table_bytes;
+  int64_t workspace_bytes;  /* artn_diag_expect and artn_diag_pair: 32 bytes per workgroup of the pass */
+  int64_t bytes_read[5];    /* per operation (ARTN_DIAG_OP_*), of the state and the values buffer; nominal */
+  int64_t bytes_written[5]; /* (ARTN_DIAG_OP_PAIR: the evolving mode; its transition-only mode writes nothing) */
+} ArtnDiagInfo;
+/* Host-only: validates, translates and groups.  Per term (n_terms entries each, any may be NULL): zmask, lo, hi and group (-1:
+ * static).  Per group (room for ARTN_DIAG_MAX_GROUPS; may be NULL): group_lo. */
+int artn_diag_query(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_terms, ArtnDiagInfo *info, uint64_t *zmask,
+                    uint64_t *lo, uint64_t *hi, int32_t *group, uint64_t *group_lo);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_diag_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, int64_t n_terms, void *table,
+                   int64_t table_bytes);
+int artn_diag_values(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_terms, const void *table, int64_t table_bytes,
+                     double *out, void *stream);
+int artn_diag_expect(const ArtnMarginalDesc *d, const void *a, const uint8_t *ops, int64_t n_terms, const void *table,
+                     int64_t table_bytes, void *ws, int64_t ws_bytes, double *out3, void *stream);
+int artn_diag_apply(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, int64_t n_terms, const void *table,
+                    int64_t table_bytes, int32_t mode, double gamma, void *stream);
+int artn_diag_pair(const ArtnMarginalDesc *d, void *lam, void *phi, const uint8_t *ops, int64_t n_terms, const void *table,
+                   int64_t table_bytes, int32_t mode, double gamma, void *ws, int64_t ws_bytes, double *out2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
