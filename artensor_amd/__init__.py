@@ -165,6 +165,16 @@ from .diagonal import (  # noqa: F401
     maxcut_terms,
     qaoa_gradient,
 )
+from . import layout  # noqa: F401
+from .layout import (  # noqa: F401
+    BitPermutation,
+    bit_permutation_info,
+    busiest_dims_order,
+    permute_dims_,
+    relayout_,
+    reverse_qubits_,
+    swap_dims_,
+)
 from .network import tn_contract  # noqa: F401
 from .statevector import state_vec  # noqa: F401
 

@@ -322,6 +322,30 @@ class ArtnDiagInfo(ctypes.Structure):
     ]
 
 
+BITPERM_MAX_BITS, BITPERM_MAX_PASSES = 40, 8
+BITPERM_TABLE_HEADER_BYTES, BITPERM_PASS_BYTES = 64, 576
+
+
+class ArtnBitpermInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_bits", ctypes.c_int32),
+        ("passes", ctypes.c_int32),
+        ("line_bits", ctypes.c_int32),
+        ("moved", ctypes.c_int32),
+        ("moved_high", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("table_bytes", ctypes.c_int64),
+        ("lds_bytes", ctypes.c_int64),
+        ("bytes_moved", ctypes.c_int64),
+        ("tile_bits", ctypes.c_int32 * 8),
+        ("grid", ctypes.c_int32 * 8),
+        ("load_degree", ctypes.c_int32 * 8),
+        ("store_degree", ctypes.c_int32 * 8),
+        ("n_tiles", ctypes.c_int64 * 8),
+        ("moved_mask", ctypes.c_uint64 * 8),
+    ]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -489,6 +513,14 @@ _EXPORTS = {
     "artn_diag_pair": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    # additive to ABI 9 as well: in-place permutations of the index bits of a state (has("artn_bitperm_apply"))
+    "artn_bitperm_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.POINTER(ArtnBitpermInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "artn_bitperm_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_int64]),
+    "artn_bitperm_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

@@ -1,5 +1,5 @@
 // artn_state_host.h -- host plumbing shared by the operations on a dense amplitude array (artn_born.hip, artn_rdm.hip,
-// artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip): the descriptor and layout checks, the max_rank rule and the
+// artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the max_rank rule and the
 // rank dispatch of the run kernels, the matrix scan, the argument checks of the pack / apply entries and the parts of a packed
 // table.  Codes and texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording
 // (`who`: "gate circuits take", ...) and its own precedence between the errors, so the pieces are separate functions.

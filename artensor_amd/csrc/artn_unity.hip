@@ -28,3 +28,4 @@
 #include "artn_measure.hip" // (artn_measure_kernel.h)
 #include "artn_channel.hip" // (artn_channel_kernel.h)
 #include "artn_diag.hip" // (artn_diag_kernel.h)
+#include "artn_bitperm.hip" // (artn_bitperm_kernel.h)

@@ -60,6 +60,26 @@ __device__ __forceinline__ wgate_f4 wgate_from_lds(const float2 *lds, int v, int
 }
 __device__ __forceinline__ wgate_d2 wgate_from_lds(const double2 *lds, int v, int) { return *(const wgate_d2 *)&lds[v]; }
 
+// The split of phases 1 and 4 as functions, for kernels that carry more than one column table (artn_bitperm_kernel.h): chunk
+// i * NT + tid of a tile is the XOR of one column per set bit; the thread's bits give a part computed once per launch, the bits
+// of i a uniform part per chunk.  `col` is indexed by tile-local bit.
+template <typename W, int LOG_NT>
+__device__ __forceinline__ uint64_t wgate_thread_cols(const uint64_t *__restrict__ col, int tid) {
+  uint64_t x = 0;
+#pragma unroll
+  for (int b = 0; b < LOG_NT; ++b)
+    if ((tid >> b) & 1) x ^= col[b + W::LOG_E];
+  return x;
+}
+template <typename W, int LOG_NT>
+__device__ __forceinline__ uint64_t wgate_chunk_cols(const uint64_t *__restrict__ col, int i) {
+  uint64_t x = 0; // (uniform)
+#pragma unroll
+  for (int b = 0; (i >> b) != 0; ++b)
+    if ((i >> b) & 1) x ^= col[b + LOG_NT + W::LOG_E];
+  return x;
+}
+
 extern __shared__ __attribute__((aligned(16))) unsigned char artn_wgate_lds[];
 
 template <typename T, int K>

@@ -1137,6 +1137,83 @@ int artn_diag_apply(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, int6
 int artn_diag_pair(const ArtnMarginalDesc *d, void *lam, void *phi, const uint8_t *ops, int64_t n_terms, const void *table,
                    int64_t table_bytes, int32_t mode, double gamma, void *ws, int64_t ws_bytes, double *out2, void *stream);
 
+/*
+ * IN-PLACE PERMUTATIONS OF THE INDEX BITS of a dense state: relayout, qubit remapping, SWAP networks and qubit reversal as pure
+ * data movement (additive to ABI 9: has("artn_bitperm_apply")).  The descriptor is a dense layout of n = 2^nb elements under the
+ * rules of the other bit-indexed families (power-of-two extents, at most 2^40 elements, a 16-byte aligned array); only n and the
+ * dtype matter: the permutation is given on MEMORY bits.  n_bits must equal nb.
+ *
+ * CONTRACT.  dst_bit[0 .. nb-1] is a permutation of 0 .. nb-1; pi(i) is the index whose bit dst_bit[b] equals bit b of i, for
+ * every b.  After the call new[pi(i)] == old[i] BIT FOR BIT for every i -- the sign of a zero, NaN payloads, denormals,
+ * infinities: no arithmetic and no conversion touches an element.  No second buffer.  The identity issues no launch.  No atomics.
+ *
+ * PLAN.  LB = 4 (complex64) or 3 (complex128) index bits of a 128-byte line; TB = ARTN_WGATE_TILE_BITS_C64 / _C128.  The host
+ * cuts the permutation into PASSES, one launch each, in order on the stream.  A pass permutes a set M of memory bits among
+ * themselves (pass_map); its TILE BITS are M, every bit below LB and the lowest other bits, min(TB, nb) in all, tile-local bit j
+ * the j-th of them ascending; so a pass moves any low bits and at most TB - LB = 8 bits at or above LB (any bits when nb <= TB).
+ * Passes come from the cycles of what is left of the permutation: a cycle that fits into the free places of the pass is taken
+ * whole (all its bits reach their final place), then at most one longer cycle gives an ARC of consecutive bits, starting at a
+ * low bit where the cycle has one, which puts all its bits but the first in their final place.  With h moved bits at or above
+ * LB: one pass when h <= 8, at most max(1, ceil((h - 1) / 7)) in general, none for the identity.  The launch of a pass walks
+ * its n >> tile_bits tiles by the hole insertion of artn_cgate_apply (segment_bits, hole_bit), in 64-bit arithmetic.
+ * LDS.  Tile-local index u is kept at LDS index L(u), the XOR of load_col[j] over the set bits j of u, L invertible; the store
+ * phase reads L(tau^-1 w) for tile-local w through store_col[j] = load_col[tau^-1 j], tau the pass's map on tile-local bits.
+ * load_degree / store_degree are the bank-conflict degrees of the two phases, 2^(dim V - rank): V the lane bits of one LDS
+ * service group of the instruction (complex64: 16 lanes of a 64-bit write = tile-local bits 1..4, 32 lanes of a 64-bit read =
+ * bits 1..5; complex128: 8 lanes of a 128-bit write = bits 0..2, the 16 lanes {0-3, 12-15, 20-27} of a 128-bit read = the span of
+ * bits 0, 1, 2 xor 3, 2 xor 4), rank that of their LDS indices modulo the banks' period in elements (16 / 32; 8 / 16).  The host searches
+ * L for load degree 1 and the least store degree.
+ *
+ * TABLE (what artn_bitperm_pack writes and the kernel reads; 8-byte little-endian fields): ArtnBitpermTable, 64 bytes, then
+ * passes x ArtnBitpermPass, 576 bytes each.
+ *
+ * ARTN_E_UNSUPPORTED: the layout and dtype refusals of the bit-indexed families, a table that is not 8-byte aligned, an array
+ * that is not 16-byte aligned.  ARTN_E_INVALID: n_bits other than log2 n, dst_bit not a permutation, a null pointer, a table
+ * smaller than the query's.
+ */
+#define ARTN_BITPERM_MAX_BITS 40
+#define ARTN_BITPERM_MAX_PASSES 8
+typedef struct ArtnBitpermPass {
+  uint64_t tile_bits, n_tiles, segment_bits, n_holes;
+  uint64_t moved_mask; /* OR of 1 << b over the memory bits the pass moves                                   */
+  uint64_t reserved[3];
+  uint64_t mem_col[16];   /* per tile-local bit j: 1 << its memory bit (0 beyond tile_bits)                   */
+  uint64_t load_col[16];  /* per tile-local bit j: what it contributes (XOR) to the LDS index, load phase     */
+  uint64_t store_col[16]; /* the same for the store phase: load_col[tau^-1 j]                                 */
+  uint64_t hole_bit[16];  /* ascending: the tile bits at or above segment_bits                                */
+} ArtnBitpermPass;
+typedef struct ArtnBitpermTable {
+  uint64_t n_passes, n_bits, reserved[6];
+} ArtnBitpermTable;
+typedef struct ArtnBitpermInfo {
+  int32_t n_bits, passes;
+  int32_t line_bits;  /* LB                                                            */
+  int32_t moved;      /* bits with dst_bit[b] != b                                     */
+  int32_t moved_high; /* h: those at or above LB                                       */
+  int32_t reserved;
+  int64_t table_bytes;
+  int64_t lds_bytes;   /* of the largest pass                                           */
+  int64_t bytes_moved; /* nominal: 2 x the state x passes                               */
+  int32_t tile_bits[ARTN_BITPERM_MAX_PASSES];
+  int32_t grid[ARTN_BITPERM_MAX_PASSES];
+  int32_t load_degree[ARTN_BITPERM_MAX_PASSES];
+  int32_t store_degree[ARTN_BITPERM_MAX_PASSES];
+  int64_t n_tiles[ARTN_BITPERM_MAX_PASSES];
+  uint64_t moved_mask[ARTN_BITPERM_MAX_PASSES];
+} ArtnBitpermInfo;
+/* Host-only: validates and plans.  Per pass p (room for ARTN_BITPERM_MAX_PASSES; any may be NULL): pass_map[p * 40 + b], the
+ * memory bit that bit b goes to in pass p (b itself outside moved_mask), b < n_bits; tiles[p * 16 + j], the memory bit of
+ * tile-local bit j (-1 beyond tile_bits); load_col / store_col [p * 16 + j]. */
+int artn_bitperm_query(const ArtnMarginalDesc *d, const int32_t *dst_bit, int32_t n_bits, ArtnBitpermInfo *info, int32_t *pass_map,
+                       int32_t *tiles, uint64_t *load_col, uint64_t *store_col);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_bitperm_pack(const ArtnMarginalDesc *d, const int32_t *dst_bit, int32_t n_bits, void *table, int64_t table_bytes);
+/* The permutation on `a`, in place: `passes` launches on `stream`, in order.  `table` is DEVICE memory holding what
+ * artn_bitperm_pack wrote for the same descriptor and dst_bit.  No allocation, copy or synchronisation.  ARTN_E_NODEVICE
+ * without a device. */
+int artn_bitperm_apply(const ArtnMarginalDesc *d, void *a, const int32_t *dst_bit, int32_t n_bits, const void *table,
+                       int64_t table_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
