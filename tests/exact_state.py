@@ -1,6 +1,8 @@
 """Integer states whose image under gates and Pauli steps is predictable EXACTLY from the memory index alone (shared by
 test_state_ops_large_cpu.py, which checks this file against the numpy oracles of the other suites, and
-test_state_ops_large_gpu.py, which uses it on states of 8 and 32 GiB).
+test_state_ops_large_gpu.py and test_wide_ops_large_gpu.py, which use it on states of 8 and 32 GiB).  A non-zero `salt` gives a
+second, unrelated integer state for the operations on two arrays; inner_sums, marginal_sums and rdm_sums are the exact integer
+values of the sums the kernels accumulate in float64; Budget and norm_invariant open and close every large GPU test.
 
 The state.  a[i] = f(i) + i g(i) with f, g in [-8, 7] from a 32-bit integer hash of the memory index i (index bits 32 and 33
 are folded in first, so every bit up to 33 matters), evaluated in torch int64; every product is formed on masked operands and
@@ -25,12 +27,18 @@ MIX = 0x45D9F3B                 # < 2^27
 HIGH = 0x27D4EB2F               # 3 * HIGH < 2^32
 LIMIT = {torch.complex64: 1 << 24, torch.complex128: 1 << 53}
 BIG = (1 << 62)
+# the salted state hashes i ^ SALT: bits 1, 6, 9 (low third of 34), 14, 19 (middle), 25, 30, 33 (top)
+SALT = (1 << 33) | (1 << 30) | (1 << 25) | (1 << 19) | (1 << 14) | (1 << 9) | (1 << 6) | (1 << 1)
 
 
-def hash_index(i):
-    """(f, g), int64 in [-8, 7], of an int64 index tensor (any values in [0, 2^34)).  Two temporaries of the size of i."""
+def hash_index(i, salt=0):
+    """(f, g), int64 in [-8, 7], of an int64 index tensor (any values in [0, 2^34)).  Two temporaries of the size of i.  A
+    non-zero salt hashes i ^ SALT instead: a second, unrelated integer state."""
     x = i & M32
     t = i >> 32
+    if salt:
+        x.bitwise_xor_(SALT & M32)
+        t.bitwise_xor_(SALT >> 32)
     t.bitwise_and_(3).mul_(HIGH)                               # bits 32, 33 -> one of four 32-bit words
     x.bitwise_xor_(t)
     for _ in range(2):
@@ -44,8 +52,10 @@ def hash_index(i):
     return t, x
 
 
-def hash_python(i):
+def hash_python(i, salt=0):
     """hash_index for one Python int, in unbounded integers."""
+    if salt:
+        i ^= SALT
     x = (i & M32) ^ (((i >> 32) & 3) * HIGH)
     for _ in range(2):
         x = ((x ^ (x >> 16)) * MIX) & M32
@@ -53,12 +63,12 @@ def hash_python(i):
     return ((x >> 5) & 15) - 8, ((x >> 21) & 15) - 8
 
 
-def fill(store, chunk=CHUNK):
-    """store (a flat complex tensor) <- the hash state, chunk by chunk."""
+def fill(store, chunk=CHUNK, salt=0):
+    """store (a flat complex tensor) <- the hash state (the salted one for salt != 0), chunk by chunk."""
     n = store.numel()
     for lo in range(0, n, chunk):
         hi = min(lo + chunk, n)
-        f, g = hash_index(torch.arange(lo, hi, device=store.device))
+        f, g = hash_index(torch.arange(lo, hi, device=store.device), salt)
         out = torch.view_as_real(store[lo:hi])
         out[:, 0].copy_(f)
         out[:, 1].copy_(g)
@@ -82,12 +92,12 @@ def _parity(p):
 class Gate:
     """(matrix, bits): bits = the MEMORY bits of the gate's dims in the order listed, the first the most significant digit of
     the row and column index.  Term t of row r is the t-th non-zero column of that row, so a signed permutation costs one
-    partner and a dense 4 x 4 four."""
+    partner, a dense 4 x 4 four and a dense gate on k = 3, 4, 5 bits 8, 16, 32."""
 
     def __init__(self, matrix, bits):
         self.bits = tuple(int(b) for b in bits)
         k = len(self.bits)
-        assert k in (1, 2) and len(set(self.bits)) == k
+        assert 1 <= k <= 5 and len(set(self.bits)) == k
         m = np.asarray(matrix, dtype=np.complex128).reshape(2 ** k, 2 ** k)
         re, im = _gauss(m, "gate")
         rows = [[c for c in range(2 ** k) if re[r, c] or im[r, c]] for r in range(2 ** k)]
@@ -164,6 +174,24 @@ class PauliSum:
         return [_string_term(c, letters, i) for c, letters in self.items]
 
 
+class Projector:
+    """|outcome><outcome| on the memory bits `bits` (the first the most significant digit): coefficient 1 where the digits of
+    the index spell `outcome`, 0 elsewhere -- what a projective channel or a post-selection without renormalisation leaves."""
+
+    def __init__(self, bits, outcome):
+        self.bits, self.outcome = tuple(int(b) for b in bits), int(outcome)
+        k = len(self.bits)
+        assert len(set(self.bits)) == k and 0 <= self.outcome < 2 ** k
+        self.T, self.growth, self.scale2 = 1, 1, None
+
+    def terms(self, i):
+        k = len(self.bits)
+        keep = torch.ones_like(i)
+        for j, b in enumerate(self.bits):
+            keep.bitwise_and_(((i >> b) & 1) ^ (1 ^ ((self.outcome >> (k - 1 - j)) & 1)))
+        return [(i, keep, 0)]
+
+
 def leaves(ops):
     """Hash evaluations per element."""
     return int(np.prod([op.T for op in ops], dtype=np.int64)) if ops else 1
@@ -200,15 +228,16 @@ def _acc(acc, term, sign=1):
     return acc.add_(term) if sign == 1 else acc.sub_(term)
 
 
-def evaluate(ops, i):
-    """(Re, Im), int64, of the state after `ops` (applied in order to the hash state) at the memory indices i."""
+def evaluate(ops, i, salt=0):
+    """(Re, Im), int64, of the state after `ops` (applied in order to the hash state, the salted one for salt != 0) at the
+    memory indices i."""
     if not ops:
-        return hash_index(i)
+        return hash_index(i, salt)
     n = i.numel()
     terms = ops[-1].terms(i)
     idx = terms[0][0] if len(terms) == 1 else torch.cat([t[0] for t in terms])
     terms = [(cre, cim) for _, cre, cim in terms]
-    re, im = evaluate(ops[:-1], idx)
+    re, im = evaluate(ops[:-1], idx, salt)
     del idx
     out_re = out_im = None
     for t, (cre, cim) in enumerate(terms):
@@ -242,27 +271,27 @@ class Tally:
         return {"compared": self.n, "bad": bad, "first_bad": int(self.first) if bad else None, "peak": int(self.peak)}
 
 
-def compare_all(store, ops, chunk=CHUNK):
-    """Every element of the flat tensor `store` against evaluate(ops, .); the chunk shrinks with the number of partners."""
+def compare_all(store, ops, chunk=CHUNK, salt=0):
+    """Every element of the flat tensor `store` against evaluate(ops, ., salt); the chunk shrinks with the number of partners."""
     n = store.numel()
     step = max(min(n, chunk // leaves(ops)), 1)
     tally = Tally(store.device)
     for lo in range(0, n, step):
         hi = min(lo + step, n)
         i = torch.arange(lo, hi, device=store.device)
-        re, im = evaluate(ops, i)
+        re, im = evaluate(ops, i, salt)
         tally.add(store[lo:hi], re, im, i)
     return tally.report()
 
 
-def compare_sample(store, ops, sample, chunk=CHUNK // 2):
+def compare_sample(store, ops, sample, chunk=CHUNK // 2, salt=0):
     """The elements of `store` at the indices `sample` (an int64 tensor on its device) against evaluate(ops, .).  (Half the chunk
     of compare_all: a deep circuit keeps the partner and coefficient tensors of every level alive at once.)"""
     step = max(min(sample.numel(), chunk // leaves(ops)), 1)
     tally = Tally(store.device)
     for lo in range(0, sample.numel(), step):
         i = sample[lo:lo + step]
-        re, im = evaluate(ops, i)
+        re, im = evaluate(ops, i, salt)
         tally.add(store[i], re, im, i)
     return tally.report()
 
@@ -276,11 +305,11 @@ def assert_exact(report, ops, dtype, label=""):
     assert report["bad"] == 0, label
 
 
-def hash_norm2(n, device, chunk=CHUNK):
+def hash_norm2(n, device, chunk=CHUNK, salt=0):
     """sum |a|^2 of the hash state of n elements, a Python int."""
     total = torch.zeros((), dtype=torch.int64, device=device)
     for lo in range(0, n, chunk):
-        f, g = hash_index(torch.arange(lo, min(lo + chunk, n), device=device))
+        f, g = hash_index(torch.arange(lo, min(lo + chunk, n), device=device), salt)
         total += (f * f).sum() + (g * g).sum()
     return int(total)
 
@@ -316,6 +345,75 @@ def expectation_sums(n, strings, device, chunk=CHUNK):
     return [(int(a), int(b)) for a, b in num], int(den)
 
 
+def inner_sums(n, ops_a, salt_a, ops_b, salt_b, M=None, device="cpu", chunk=CHUNK):
+    """(Re, Im) of sum_i conj(A[i]) (M B)[i] over n elements, Python ints: A = ops_a on the hash state of salt_a, B = ops_b on
+    that of salt_b, M an optional Gate (or any op) applied to B.  Chunked int64 sums; sum_i (|Re A| + |Im A|)(|Re B| + |Im B|)
+    bounds every partial sum of either part in any order and has to stay below 2^53."""
+    ops_a, ops_b = list(ops_a), list(ops_b) + ([M] if M is not None else [])
+    step = max(min(n, chunk // max(leaves(ops_a), leaves(ops_b))), 1)
+    re = im = cover = 0
+    for lo in range(0, n, step):
+        i = torch.arange(lo, min(lo + step, n), device=device)
+        ar, ai = evaluate(ops_a, i, salt_a)
+        br, bi = evaluate(ops_b, i, salt_b)
+        re += int((ar * br).sum() + (ai * bi).sum())               # conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
+        im += int((ar * bi).sum() - (ai * br).sum())
+        cover += int(((ar.abs() + ai.abs()) * (br.abs() + bi.abs())).sum())
+    assert cover < 1 << 53, f"partial sums up to {cover} are not exact in float64"
+    return re, im
+
+
+def _digits(i, bits):
+    """The digit class of the indices i: the value of the memory bits `bits`, the first the most significant."""
+    k = len(bits)
+    r = torch.zeros_like(i)
+    for j, b in enumerate(bits):
+        r.bitwise_or_(((i >> b) & 1) << (k - 1 - j))
+    return r
+
+
+def marginal_sums(n, bits, device="cpu", chunk=CHUNK):
+    """The 2^k Python ints sum |a|^2 of the hash state of n elements per digit class of the memory bits `bits` (the first the
+    most significant digit).  Their total, which bounds every partial sum, has to stay below 2^53."""
+    bits = [int(b) for b in bits]
+    out = torch.zeros(2 ** len(bits), dtype=torch.int64, device=device)
+    for lo in range(0, n, chunk):
+        i = torch.arange(lo, min(lo + chunk, n), device=device)
+        f, g = hash_index(i)
+        out.index_add_(0, _digits(i, bits), f.mul_(f).add_(g.mul_(g)))
+    out = [int(v) for v in out.cpu().tolist()]
+    assert sum(out) < 1 << 53
+    return out
+
+
+def rdm_sums(n, bits, device="cpu", chunk=CHUNK):
+    """(Re, Im), two 2^k x 2^k lists of Python ints, of rho[i, j] = sum_r a[i, r] conj(a[j, r]) of the hash state of n elements:
+    i, j the digit classes of the memory bits `bits` (the first the most significant digit), r every other bit.  Per chunk of r
+    the four products F F^T, G G^T, G F^T, F G^T are float64 matrix products of integers in [-8, 7] over at most 2^25 / 2^k
+    columns -- partial sums below 2^31, exact -- and the chunks are added in int64.  |rho[i, j]| and every partial sum of it are
+    bounded by the trace, which has to stay below 2^53."""
+    bits = [int(b) for b in bits]
+    k, D = len(bits), 2 ** len(bits)
+    spread = torch.tensor([sum(((c >> (k - 1 - j)) & 1) << b for j, b in enumerate(bits)) for c in range(D)], dtype=torch.int64,
+                          device=device)
+    rest = n >> k
+    step = max(min(rest, chunk // D), 1)
+    re = torch.zeros((D, D), dtype=torch.int64, device=device)
+    im = torch.zeros((D, D), dtype=torch.int64, device=device)
+    for lo in range(0, rest, step):
+        r = torch.arange(lo, min(lo + step, rest), device=device)
+        for b in sorted(bits):                                      # a zero at every kept bit, from the lowest up
+            r = ((r >> b) << (b + 1)) | (r & ((1 << b) - 1))
+        f, g = hash_index((spread[:, None] | r[None, :]).reshape(-1))
+        f, g = f.view(D, -1).double(), g.view(D, -1).double()
+        re += (f @ f.T + g @ g.T).to(torch.int64)                   # a conj(b) = (fa fb + ga gb) + i (ga fb - fa gb)
+        gf = g @ f.T
+        im += (gf - gf.T).to(torch.int64)
+    re, im = re.cpu().tolist(), im.cpu().tolist()
+    assert sum(re[c][c] for c in range(D)) < 1 << 53
+    return re, im
+
+
 def sample_indices(n, elem_size, count, seed=1):
     """int64 CPU tensor of `count` distinct memory indices below n: the first and the last tile of 1024 elements, the 2048
     elements on either side of byte offsets 2^31 and 2^32 and of element index 2^31 (where the array reaches them), the rest
@@ -331,6 +429,51 @@ def sample_indices(n, elem_size, count, seed=1):
     uniq, first = np.unique(both.numpy(), return_index=True)
     keep = np.sort(first)[:max(count, must.numel())]              # the edges first, then random indices in drawing order
     return both[torch.from_numpy(keep)]
+
+
+# ---- what every large-state GPU test begins and ends with ---------------------------------------------------------------------
+DEV = "cuda:0"
+GIB = 1 << 30
+SIZES = {"c64-n30": (torch.complex64, 30), "c128-n29": (torch.complex128, 29), "c64-n32": (torch.complex64, 32)}
+
+
+class Budget:
+    """The hash state of one size and the memory it may cost: the state (`arrays` of them) plus 4 GiB."""
+
+    def __init__(self, size, arrays=1):
+        import pytest
+        self.dtype, self.n = SIZES[size]
+        self.size = size
+        elem = 8 if self.dtype == torch.complex64 else 16
+        self.allowed = arrays * (elem << self.n) + 4 * GIB
+        torch.cuda.empty_cache()
+        free, _ = torch.cuda.mem_get_info(torch.device(DEV))
+        if free < self.allowed:
+            pytest.skip(f"needs {self.allowed / GIB:.1f} GiB of free device memory ({arrays} array(s) of {(elem << self.n) / GIB:.0f} GiB "
+                        f"and 4 GiB of chunk temporaries), {free / GIB:.1f} GiB free")
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        self.before = torch.cuda.memory_allocated()
+        self.store = fill(torch.empty(1 << self.n, dtype=self.dtype, device=DEV))
+
+    def view(self):
+        return self.store.view((2,) * self.n)
+
+    def close(self, label):
+        torch.cuda.synchronize()
+        rise = torch.cuda.max_memory_allocated() - self.before
+        print(f"{label}: peak device memory {rise / GIB:.2f} GiB, allowed {self.allowed / GIB:.2f} GiB")
+        self.store = None
+        torch.cuda.empty_cache()
+        assert rise <= self.allowed, label
+
+
+def norm_invariant(b, ops, label):
+    import artensor_amd as A
+    want = scale2(ops) * hash_norm2(1 << b.n, DEV)
+    got = A.norm2(b.store)
+    print(f"{label}: norm2 {got!r}, scale2 {scale2(ops)} * sum |hash|^2 = {want} ({want / 2 ** 53:.3f} of 2^53)")
+    assert want < 1 << 53 and got == float(want), label
 
 
 # ---- the circuits of the large-state tests, written on MEMORY bits -----------------------------------------------------------
@@ -462,3 +605,103 @@ def expectation_batch(n):
     """17 strings of one group (equal flip positions): a second pass runs."""
     rng = np.random.default_rng(5000 + n)
     return [random_letters(rng, n, (n - 1, 24, 5, 1)) for _ in range(17)]
+
+
+# ---- the wide gates, channels and two-state circuits of test_wide_ops_large_gpu.py -------------------------------------------
+TOFFOLI = np.eye(8)[[0, 1, 2, 3, 4, 5, 7, 6]].astype(np.complex128)        # controls: the first two listed bits
+FREDKIN = np.eye(8)[[0, 1, 2, 3, 4, 6, 5, 7]].astype(np.complex128)        # control: the first listed bit
+CCZ = np.diag([1, 1, 1, 1, 1, 1, 1, -1]).astype(np.complex128)
+XZY = np.kron(X, np.kron(Z, Y))
+PERM8 = (0, 7, 1, 6, 2, 4, 3, 5)
+
+
+def _conjugated(m, perm):
+    out = np.zeros_like(m)
+    out[np.ix_(perm, perm)] = m
+    return out
+
+
+def _rows_shuffled(m, a, c):
+    """Row r of the result is row (a r + c) mod 2^k of m (a odd): a permutation times m."""
+    return m[[(a * r + c) % m.shape[0] for r in range(m.shape[0])]]
+
+
+def _kron(*ms):
+    out = np.eye(1, dtype=np.complex128)
+    for m in ms:
+        out = np.kron(out, m)
+    return out
+
+
+# two non-zeros per row (growth 5), asymmetric, and no Kronecker product: the partner of a row differs from it in 2 or 3 digits
+PAIR3 = _conjugated(np.kron(np.eye(4), G1), PERM8)
+# dense Gaussian-integer multiples of unitaries on 3, 4, 5 bits: ONE factor with components up to 2, so every component lies in
+# {-2..2} (x 1 or i); scale2 20 40 80, growth 12 24 48; the row shuffle makes them no Kronecker products
+W3 = _rows_shuffled(_kron(U5, U2, V2), 3, 5)
+W4 = _rows_shuffled(_kron(U5.T, U2, V2, U2.T), 7, 3)
+W5 = _rows_shuffled(_kron(U5, U2.T, V2.T, U2, V2), 11, 13)
+WIDE = {3: W3, 4: W4, 5: W5}
+
+
+def wide_whole_cases(n):
+    """name -> gates on memory bits, ONE CALL EACH, every element compared (at most 4 hash evaluations per element)."""
+    t, u = n - 1, n - 2
+    return {
+        "toffoli": [(TOFFOLI, (t, 3, u))],
+        "fredkin": [(FREDKIN, (5, t, 12))],
+        "ccz": [(CCZ, (u, t, 0))],
+        "pair3": [(PAIR3, (t, 13, 1)), (PAIR3, (1, 13, t))],                # the second call in reversed target order
+    }
+
+
+def wide_sampled_cases(n):
+    """(k, where) -> target bits of the dense gate WIDE[k]: all above the tile of 2^12 / 2^11 elements, all inside it, mixed (at
+    n = 32 the mixed sets hold bits 31 and 30, on either side of element index 2^31)."""
+    t, u = n - 1, n - 2
+    return {
+        (3, "above"): (t, 20, u), (4, "above"): (u, 25, t, 14), (5, "above"): (22, t, 13, u, 17),
+        (3, "inside"): (2, 9, 0), (4, "inside"): (7, 1, 10, 4), (5, "inside"): (3, 10, 0, 8, 5),
+        (3, "mixed"): (t, 6, u), (4, "mixed"): (u, 2, t, 15), (5, "mixed"): (9, t, 19, 0, u),
+    }
+
+
+def wide_fused_parts(n):
+    """Eight parts: four stretches of two or three signed-permutation gates of fused_gates alternating with the wide gates W3,
+    W4, W5 and a Fredkin.  Three dense gates: 8 * 16 * 32 = 2^12 hash evaluations per element, scale2 20 * 40 * 80 = 64 000,
+    growth 12 * 24 * 48."""
+    t, u = n - 1, n - 2
+    g = fused_gates(n)
+    return [[g[0], g[2], g[3]], (W3, (t, 13, 1)), [g[6], g[7]], (W4, (4, u, 23, t)), [g[8], g[9], g[11]],
+            (W5, (u, 7, t, 0, 26)), [g[12], g[14]], (FREDKIN, (24, t, 2))]
+
+
+def wide_fused_gates(n):
+    return [x for part in wide_fused_parts(n) for x in (part if isinstance(part, list) else [part])]
+
+
+CHANNEL_PROBS = [0.4, 0.3, 0.2, 0.1]
+CHANNEL_UNITARIES = [np.eye(8, dtype=np.complex128), TOFFOLI, XZY, FREDKIN]
+MEASURE1 = np.array([[2, 1j], [-1 + 1j, 1]])                               # the measured matrices of the pair circuit
+MEASURE2 = np.array([[2, 0, 1j, 0], [0, 1 - 1j, 0, -1], [0, -2j, 1, 0], [1, 0, 0, 1j]])
+
+
+def pair_gates(n):
+    t, u = n - 1, n - 2
+    return [(G2, (t, 5)), (G1, (u,)), (CNOT, (3, t))], [None, MEASURE1, MEASURE2]
+
+
+def pair_max_ranks(dtype):
+    """The max_rank values of the two-state cases: the default and 0, and for complex128 (whose two-state default is 1, cut
+    like 0 for these circuits) also 2, the plan that fuses the steps on the two top bits into one run."""
+    return [None, 0] if dtype == torch.complex64 else [None, 0, 2]
+
+
+def bits_of(view, dims):
+    """Memory bits of the dims of a [2]*n view, from its strides."""
+    return tuple(int(view.stride(d)).bit_length() - 1 for d in dims)
+
+
+def dims_on(view, bits):
+    """The dims of a [2]*n view that lie on the memory bits `bits`."""
+    where = {int(view.stride(d)).bit_length() - 1: d for d in range(view.dim())}
+    return tuple(where[b] for b in bits)

@@ -26,6 +26,7 @@ import torch
 
 import artensor_amd as A
 import exact_state as E
+from exact_state import Budget, norm_invariant
 
 pytestmark = pytest.mark.gpu
 
@@ -35,43 +36,6 @@ SIZES = {"c64-n30": (torch.complex64, 30), "c128-n29": (torch.complex128, 29), "
 IN_PLACE = list(SIZES)
 OUT_OF_PLACE = ["c64-n30", "c128-n29"]                                   # y = H a needs a second array: the 8 GiB sizes
 SAMPLE = 1 << 18
-
-
-class Budget:
-    """The hash state of one size and the memory it may cost: the state (`arrays` of them) plus 4 GiB."""
-
-    def __init__(self, size, arrays=1):
-        self.dtype, self.n = SIZES[size]
-        self.size = size
-        elem = 8 if self.dtype == torch.complex64 else 16
-        self.allowed = arrays * (elem << self.n) + 4 * GIB
-        torch.cuda.empty_cache()
-        free, _ = torch.cuda.mem_get_info(torch.device(DEV))
-        if free < self.allowed:
-            pytest.skip(f"needs {self.allowed / GIB:.1f} GiB of free device memory ({arrays} array(s) of {(elem << self.n) / GIB:.0f} GiB "
-                        f"and 4 GiB of chunk temporaries), {free / GIB:.1f} GiB free")
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        self.before = torch.cuda.memory_allocated()
-        self.store = E.fill(torch.empty(1 << self.n, dtype=self.dtype, device=DEV))
-
-    def view(self):
-        return self.store.view((2,) * self.n)
-
-    def close(self, label):
-        torch.cuda.synchronize()
-        rise = torch.cuda.max_memory_allocated() - self.before
-        print(f"{label}: peak device memory {rise / GIB:.2f} GiB, allowed {self.allowed / GIB:.2f} GiB")
-        self.store = None
-        torch.cuda.empty_cache()
-        assert rise <= self.allowed, label
-
-
-def norm_invariant(b, ops, label):
-    want = E.scale2(ops) * E.hash_norm2(1 << b.n, DEV)
-    got = A.norm2(b.store)
-    print(f"{label}: norm2 {got!r}, scale2 {E.scale2(ops)} * sum |hash|^2 = {want} ({want / 2 ** 53:.3f} of 2^53)")
-    assert want < 1 << 53 and got == float(want), label
 
 
 # ---- gates --------------------------------------------------------------------------------------------------------------------
