@@ -30,7 +30,17 @@ def rnd(gen, shape):
     return torch.view_as_complex(x).contiguous()
 
 
-def main(cases=300, seed=0):
+def exact_ops(rng, eq, sa, sb):
+    """exact=True: operands from the generators of tests/exact_contraction.py (Gaussian integers, every partial sum exact in
+    fp32: draw_chain sizes the streamed operand by the worst-case bound of the step), on the device; class wide / dense by turns"""
+    if "exact_contraction" not in sys.modules:   # (exact=True only: the default run imports nothing from tests/)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import exact_contraction as X
+    a, (b,) = X.draw_chain(int(rng.integers(1 << 30)), "wide" if rng.random() < 0.5 else "dense", "complex64", [(eq, sb)], sa)
+    return torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+
+
+def main(cases=300, seed=0, exact=False):
     rng = np.random.default_rng(seed)
     gen = torch.Generator(device="cuda").manual_seed(seed)
     seen, worst, t0 = collections.Counter(), 0.0, time.time()
@@ -68,13 +78,15 @@ def main(cases=300, seed=0):
             path = "xgemm+tail" if blocks >= 4 and blocks % 3 and rt * (blocks // 3) >= 2048 else "xgemm"
         else:
             path = {0: "strided"}.get(info["kernel"], f"kernel{info['kernel']}")
-        a, b = rnd(gen, sa), rnd(gen, sb)
+        a, b = exact_ops(rng, eq, sa, sb) if exact else (rnd(gen, sa), rnd(gen, sb))
         got = A.contract(eq, a, b)
         sym = {x: chr(65 + i) if i < 26 else chr(97 + i - 26) for i, x in enumerate(ext)}
         want = torch.einsum("".join(sym[x] for x in la) + "," + "".join(sym[x] for x in lb) + "->" + "".join(sym[x] for x in lo),
                             a.to(torch.complex128), b.to(torch.complex128))
         err = float((got.to(torch.complex128) - want).abs().max() / want.abs().max())
         tol = 3e-6 * max(1.0, float(np.prod(list(K.values()))) / 256.0) ** 0.5
+        if exact:   # (complex128 einsum of integers below 2^24: the exact result; `==`, not a tolerance)
+            tol = 0.0 if torch.equal(got.to(torch.complex128), want) else -1.0
         if not err <= tol:
             print("FAIL", case, fam, eq, sa, sb, err, tol, info)
             return 1

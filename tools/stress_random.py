@@ -13,7 +13,24 @@ def rnd(gen, shape, dtype):
     x = torch.randn(tuple(shape) + (2,), device="cuda", generator=gen, dtype=torch.float64)
     return torch.view_as_complex(x).to(dtype).contiguous()
 
-def main(cases=200, seed=0):
+def _exact_module():
+    """tests/exact_contraction.py, found once (exact=True only: the default run imports nothing from tests/)"""
+    if "exact_contraction" not in sys.modules:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import exact_contraction
+    return exact_contraction
+
+def exact_ops(rng, dtype, stages, a_shape):
+    """exact=True: operands of a chain of steps from the generators of tests/exact_contraction.py (Gaussian integers, every
+    partial sum exact in the accumulator: draw_chain
+    sizes the streamed operand by the worst-case bound of every stage), on the device; class wide / dense by turns, wide128 for complex128"""
+    X = _exact_module()
+    kind = "complex128" if dtype == torch.complex128 else "complex64"
+    cls = ("wide128" if kind == "complex128" else "wide") if rng.random() < 0.5 else "dense"
+    a, smalls = X.draw_chain(int(rng.integers(1 << 30)), cls, kind, stages, a_shape)
+    return torch.from_numpy(a).cuda(), [torch.from_numpy(b).cuda() for b in smalls]
+
+def main(cases=200, seed=0, exact=False):
     rng = np.random.default_rng(seed)
     gen = torch.Generator(device="cuda").manual_seed(seed)
     worst = {torch.complex64: 0.0, torch.complex128: 0.0}
@@ -44,8 +61,11 @@ def main(cases=200, seed=0):
         eq1 = "".join(la_) + "," + "".join(lb1_) + "->" + "".join(lo1_)
         if kind == "gather":
             na, nb = int(rng.integers(1, 12)), int(rng.integers(1, 12))
-            a = rnd(gen, (na,) + ext(la_)[1:], dtype)
-            b = rnd(gen, (nb,) + ext(lb1_)[1:], dtype)
+            if exact:
+                a, (b,) = exact_ops(rng, dtype, [(eq1, (nb,) + ext(lb1_)[1:])], (na,) + ext(la_)[1:])
+            else:
+                a = rnd(gen, (na,) + ext(la_)[1:], dtype)
+                b = rnd(gen, (nb,) + ext(lb1_)[1:], dtype)
             ia, ib = torch.from_numpy(rng.integers(0, na, size=batch)), torch.from_numpy(rng.integers(0, nb, size=batch))
             got = C.contract_gathered(eq1, a, ia, b, ib)
             want = torch.einsum(eq1, a.cpu()[ia].to(torch.complex128), b.cpu()[ib].to(torch.complex128))
@@ -53,7 +73,10 @@ def main(cases=200, seed=0):
                 got = A.contract(eq1, a[ia.cuda()].contiguous(), b[ib.cuda()].contiguous())
             kinds["gather"] += 1
         else:
-            a, b1 = rnd(gen, ext(la_), dtype), rnd(gen, ext(lb1_), dtype)
+            if exact and kind == "single":
+                a, (b1,) = exact_ops(rng, dtype, [(eq1, ext(lb1_))], ext(la_))
+            elif not exact:
+                a, b1 = rnd(gen, ext(la_), dtype), rnd(gen, ext(lb1_), dtype)
             if kind == "single":
                 got = A.contract(eq1, a, b1)
                 want = torch.einsum(eq1, a.cpu().to(torch.complex128), b1.cpu().to(torch.complex128))
@@ -72,7 +95,10 @@ def main(cases=200, seed=0):
                 rng.shuffle(lo2)
                 lb2_, lo2_ = (["z"] + lb2, ["z"] + lo2) if batch and rng.random() < 0.5 else (lb2, (["z"] if batch else []) + lo2)
                 eq2 = "".join(lo1_) + "," + "".join(lb2_) + "->" + "".join(lo2_)
-                b2 = rnd(gen, ext(lb2_), dtype)
+                if exact:
+                    a, (b1, b2) = exact_ops(rng, dtype, [(eq1, ext(lb1_)), (eq2, ext(lb2_))], ext(la_))
+                else:
+                    b2 = rnd(gen, ext(lb2_), dtype)
                 got = C.contract2(eq1, a, b1, eq2, b2)
                 kinds["pair"] += 1
                 if got is None:
@@ -82,6 +108,8 @@ def main(cases=200, seed=0):
                 want = torch.einsum(eq2, torch.einsum(eq1, a.cpu().to(torch.complex128), b1.cpu().to(torch.complex128)), b2.cpu().to(torch.complex128))
         err = float((got.cpu().to(torch.complex128) - want).abs().max() / want.abs().max())
         worst[dtype] = max(worst[dtype], err)
+        if exact:   # (complex128 einsum of integers below 2^53: the exact result; `==`, not a tolerance)
+            tol = 0.0 if torch.equal(got.cpu().to(torch.complex128), want) else -1.0
         if not err <= tol:
             print("FAIL", kind, dtype, eq1, locals().get("eq2"), "batch", batch, "err", err)
             return 1
