@@ -11,31 +11,14 @@
 #include "artn_state_host.h"
 #include "artn_cgate_kernel.h"
 
-struct CgatePlan {
-  int t = 0, c = 0, n_bits = 0, tb = 0, seg_bits = 0;
-  std::vector<int> target;  // memory bits in the order listed
+struct CgatePlan : TilePlan {
+  int t = 0, c = 0, n_bits = 0;
   std::vector<int> control; // memory bits in the order listed
   std::vector<int> value;   // the wanted digit of each control
-  std::vector<int> tile;    // tile bits, ascending
   std::vector<int> hole;    // hole bits, ascending
   uint64_t high_mask = 0, high_want = 0, low_mask = 0, low_want = 0; // over memory bits
   ArtnCgateInfo info = {};
 };
-
-// one listed dimension of a gate: in range, of extent 2, not listed before among `seen`
-static int cgate_dim(const ArtnMarginalDesc *d, int32_t dim, const std::vector<int32_t> &seen, size_t n_targets, bool is_control) {
-  if (dim < 0 || dim >= d->n_dims) return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " out of range");
-  if (d->extent[dim] != 2)
-    return fail(ARTN_E_INVALID, "gates act on dimensions of extent 2; dimension " + std::to_string(dim) + " has extent " +
-                                    std::to_string(d->extent[dim]));
-  for (size_t i = 0; i < seen.size(); ++i)
-    if (seen[i] == dim) {
-      if (is_control && i < n_targets)
-        return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " is both a target and a control");
-      return fail(ARTN_E_INVALID, "the dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
-    }
-  return ARTN_OK;
-}
 
 // The layout checks of artn_wgate_query, then targets, controls, their classes, the tile and the holes (include/artn.h: PLAN).
 // `mat` may be null (artn_cgate_apply: the matrix is in the table); the flag "diagonal" is then not set.
@@ -58,13 +41,13 @@ static int cgate_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *targe
   const int lb = d->dtype == ARTN_C64 ? 4 : 3; // index bits of a 128-byte line
   std::vector<int32_t> seen;
   for (int j = 0; j < t; ++j) {
-    if (int rc = cgate_dim(d, targets[j], seen, (size_t)t, false)) return rc;
+    if (int rc = state_tile_dim(d, targets[j], seen, (size_t)t, false, "gates")) return rc;
     seen.push_back(targets[j]);
     cp.target.push_back(__builtin_ctzll((uint64_t)d->stride[targets[j]]));
   }
   int c_high = 0;
   for (int j = 0; j < c; ++j) {
-    if (int rc = cgate_dim(d, controls[j], seen, (size_t)t, true)) return rc;
+    if (int rc = state_tile_dim(d, controls[j], seen, (size_t)t, true, "gates")) return rc;
     seen.push_back(controls[j]);
     const int v = values ? values[j] : 1;
     if (v != 0 && v != 1)
@@ -76,29 +59,17 @@ static int cgate_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *targe
   }
   bool diagonal = false;
   if (mat && !state_matrix_scan(mat, 1 << t, diagonal)) return fail(ARTN_E_INVALID, "a matrix entry is not finite");
-  const int tb_max = d->dtype == ARTN_C64 ? ARTN_WGATE_TILE_BITS_C64 : ARTN_WGATE_TILE_BITS_C128;
-  const int sub_bits = n_bits - c_high;
-  cp.tb = std::min(tb_max, sub_bits);
-  uint64_t target_mask = 0;
-  for (int b : cp.target) target_mask |= (uint64_t)1 << b;
-  cp.tile = cp.target;
-  for (int b = 0; (int)cp.tile.size() < cp.tb; ++b)
-    if (!(((target_mask | cp.high_mask) >> b) & 1)) cp.tile.push_back(b);
-  std::sort(cp.tile.begin(), cp.tile.end());
-  cp.seg_bits = 0;
-  while (cp.seg_bits < cp.tb && cp.tile[cp.seg_bits] == cp.seg_bits) ++cp.seg_bits;
+  state_tile_plan(d->dtype, n_bits - c_high, cp.high_mask, cp);
   for (int j = cp.seg_bits; j < cp.tb; ++j) cp.hole.push_back(cp.tile[j]);
   for (int b = 0; b < n_bits; ++b)
     if ((cp.high_mask >> b) & 1) cp.hole.push_back(b);
   std::sort(cp.hole.begin(), cp.hole.end());
   if ((int)cp.hole.size() > ARTN_CGATE_MAX_HOLES) return fail(ARTN_E_UNSUPPORTED, "controlled gates take at most 2^40 elements");
-  const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16;
   cp.info.t = t, cp.info.c = c, cp.info.c_high = c_high, cp.info.c_low = c - c_high;
   cp.info.tile_bits = cp.tb, cp.info.diagonal = diagonal ? 1 : 0;
-  cp.info.n_selected = n >> c, cp.info.n_tiles = (n >> c_high) >> cp.tb, cp.info.segment = (int64_t)1 << cp.seg_bits;
-  cp.info.lds_bytes = elem << cp.tb;
+  cp.info.n_selected = n >> c, cp.info.n_tiles = cp.n_tiles, cp.info.segment = cp.segment, cp.info.lds_bytes = cp.lds_bytes;
   cp.info.table_bytes = (int64_t)sizeof(ArtnCgateTable) + ((int64_t)16 << (2 * t));
-  cp.info.bytes_read = cp.info.bytes_written = (n >> c_high) * elem;
+  cp.info.bytes_read = cp.info.bytes_written = (n >> c_high) * cp.elem;
   return ARTN_OK;
 }
 
@@ -109,13 +80,9 @@ static void cgate_launch(const CgatePlan &cp, T *a, const void *table, const voi
   const long long m = (long long)mask, v = (long long)value;
   const dim3 grid((unsigned)std::min<int64_t>(cp.info.n_tiles, ARTN_WGATE_MAX_GRID)), block(ARTN_BORN_THREADS);
   const size_t lds = (size_t)cp.info.lds_bytes;
-  switch (cp.t) {
-  case 1: hipLaunchKernelGGL((artn_k_cgate<T, 1>), grid, block, lds, st, a, tab, cnd, m, v); break;
-  case 2: hipLaunchKernelGGL((artn_k_cgate<T, 2>), grid, block, lds, st, a, tab, cnd, m, v); break;
-  case 3: hipLaunchKernelGGL((artn_k_cgate<T, 3>), grid, block, lds, st, a, tab, cnd, m, v); break;
-  case 4: hipLaunchKernelGGL((artn_k_cgate<T, 4>), grid, block, lds, st, a, tab, cnd, m, v); break;
-  case 5: hipLaunchKernelGGL((artn_k_cgate<T, 5>), grid, block, lds, st, a, tab, cnd, m, v); break;
-  }
+  state_with_k(cp.t, [&](auto k) {
+    hipLaunchKernelGGL((artn_k_cgate<T, decltype(k)::value>), grid, block, lds, st, a, tab, cnd, m, v);
+  });
 }
 
 extern "C" {
@@ -148,34 +115,13 @@ int artn_cgate_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets
   tab.flags = cp.info.diagonal ? ARTN_GATE_DIAGONAL : 0, tab.group_bits = (uint64_t)gb, tab.segment_bits = (uint64_t)cp.seg_bits;
   tab.n_holes = (uint64_t)cp.hole.size(), tab.high_want = cp.high_want, tab.high_mask = cp.high_mask;
   for (size_t j = 0; j < cp.hole.size(); ++j) tab.hole_bit[j] = (uint64_t)cp.hole[j];
-  // the swizzle of artn_wgate_pack: the window is the lowest P = min(6, gb) tile-local bits; its non-targets are group bits
-  // 0 .. P-j-1 and LDS index bits of the same number, its j targets get the LDS index bits P-j .. P-1
-  const int window = std::min(6, gb);
-  int low_targets = 0;
-  for (int p = 0; p < window; ++p)
-    if (std::find(cp.target.begin(), cp.target.end(), cp.tile[p]) != cp.target.end()) ++low_targets;
-  int rank = 0, seen = 0; // non-targets / window targets below the position
-  for (int p = 0; p < cp.tb; ++p) {
-    tab.mem_col[p] = (uint64_t)1 << cp.tile[p];
-    const auto at = std::find(cp.target.begin(), cp.target.end(), cp.tile[p]);
-    if (at == cp.target.end()) {
-      if ((cp.low_mask >> cp.tile[p]) & 1) { // a low control: group bit `rank`
-        tab.group_mask |= (uint64_t)1 << rank;
-        tab.group_want |= ((cp.low_want >> cp.tile[p]) & 1) << rank;
-      }
-      tab.lds_col[p] = (uint64_t)1 << rank++;
-      continue;
+  state_tile_cols(cp, tab.mem_col, tab.lds_col, tab.target_bit, tab.target_pos, tab.swizzle);
+  for (int p = 0; p < cp.tb; ++p) // a low control is a non-target tile bit, so a group bit: the one its lds_col names
+    if ((cp.low_mask >> cp.tile[p]) & 1) {
+      tab.group_mask |= tab.lds_col[p];
+      if ((cp.low_want >> cp.tile[p]) & 1) tab.group_want |= tab.lds_col[p];
     }
-    const int listed = (int)(at - cp.target.begin()), row_bit = t - 1 - listed; // the LAST listed target is row bit 0
-    tab.target_bit[listed] = (uint64_t)cp.tile[p], tab.target_pos[listed] = (uint64_t)p;
-    if (p < window) tab.swizzle[row_bit] = (uint64_t)1 << (window - low_targets + seen++);
-    tab.lds_col[p] = ((uint64_t)1 << (gb + row_bit)) ^ tab.swizzle[row_bit];
-  }
-  const int r = std::min(rows, ARTN_WGATE_ROWS), nb = rows / r;
-  for (int row = 0; row < rows; ++row)
-    for (int col = 0; col < rows; ++col)
-      if (mat[2 * (row * rows + col)] != 0.0 || mat[2 * (row * rows + col) + 1] != 0.0)
-        tab.block_mask |= (uint64_t)1 << ((row / r) * nb + col / r);
+  tab.block_mask = state_block_mask(mat, rows);
   *(ArtnCgateTable *)table = tab;
   std::copy(mat, mat + 2 * rows * rows, (double *)((ArtnCgateTable *)table + 1));
   return ARTN_OK;

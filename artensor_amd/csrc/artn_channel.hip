@@ -14,10 +14,8 @@
 static_assert(sizeof(ArtnChannelTable) == 512 && sizeof(ArtnChannelOp) == 16, "the table's header and operator records");
 static_assert(sizeof(ArtnChannelRecord) == ARTN_MEASURE_RECORD_BYTES, "int64 outcome, then probability, total and scale");
 
-struct ChannelPlan {
-  int t = 0, m = 0, form = 0, n_bits = 0, tb = 0, seg_bits = 0;
-  std::vector<int> target; // memory bits in the order listed
-  std::vector<int> tile;   // tile bits, ascending
+struct ChannelPlan : TilePlan {
+  int t = 0, m = 0, form = 0, n_bits = 0;
   ArtnChannelInfo info = {};
 };
 
@@ -48,7 +46,6 @@ static int channel_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *dim
                         ChannelPlan &cp) {
   if (int rc = state_desc(d, "channels take", ARTN_MARG_MAX_DIMS, false)) return rc;
   if (!dims) return fail(ARTN_E_INVALID, "null pointer");
-  const int nd = d->n_dims;
   StateLayout l;
   if (int rc = state_layout(d, l)) return rc;
   if (int rc = state_bits_only(l, "channels take")) return rc;
@@ -60,16 +57,7 @@ static int channel_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *dim
     return fail(ARTN_E_INVALID, "a channel on " + std::to_string(t) + " dimensions needs a state of at least 2^" + std::to_string(t) +
                                     " elements; this one has " + std::to_string((long long)n));
   cp.t = t, cp.m = m, cp.form = form, cp.n_bits = n_bits;
-  for (int j = 0; j < t; ++j) {
-    const int32_t dim = dims[j];
-    if (dim < 0 || dim >= nd) return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " out of range");
-    if (d->extent[dim] != 2)
-      return fail(ARTN_E_INVALID, "channels act on dimensions of extent 2; dimension " + std::to_string(dim) + " has extent " +
-                                      std::to_string(d->extent[dim]));
-    for (int i = 0; i < j; ++i)
-      if (dims[i] == dim) return fail(ARTN_E_INVALID, "the dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
-    cp.target.push_back(__builtin_ctzll((uint64_t)d->stride[dim]));
-  }
+  if (int rc = state_tile_targets(d, t, dims, "channels", cp.target)) return rc;
   if (int rc = channel_counts(t, m, form)) return rc;
   if (mats)
     for (int j = 0; j < m; ++j) {
@@ -77,22 +65,14 @@ static int channel_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *dim
       if (!state_matrix_scan(mats + ((size_t)j << (2 * t + 1)), 1 << t, diagonal))
         return fail(ARTN_E_INVALID, "an entry of operator " + std::to_string(j) + " is not finite");
     }
-  const int tb_max = d->dtype == ARTN_C64 ? ARTN_WGATE_TILE_BITS_C64 : ARTN_WGATE_TILE_BITS_C128;
-  cp.tb = std::min(tb_max, n_bits);
-  cp.tile = cp.target;
-  for (int b = 0; (int)cp.tile.size() < cp.tb; ++b)
-    if (std::find(cp.target.begin(), cp.target.end(), b) == cp.target.end()) cp.tile.push_back(b);
-  std::sort(cp.tile.begin(), cp.tile.end());
-  cp.seg_bits = 0;
-  while (cp.seg_bits < cp.tb && cp.tile[cp.seg_bits] == cp.seg_bits) ++cp.seg_bits;
-  const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16;
+  state_tile_plan(d->dtype, n_bits, 0, cp);
   ArtnChannelInfo &ci = cp.info;
   ci.t = t, ci.m = m, ci.form = form, ci.tile_bits = cp.tb;
   for (int f = 0; f < 3; ++f) ci.launches[f] = 2, ci.reduction[f] = f;
-  ci.n_tiles = n >> cp.tb, ci.segment = (int64_t)1 << cp.seg_bits, ci.lds_bytes = elem << cp.tb;
+  ci.n_tiles = cp.n_tiles, ci.segment = cp.segment, ci.lds_bytes = cp.lds_bytes;
   ci.weight_doubles = channel_weight_doubles(form, t);
   ci.table_bytes = channel_table_bytes(t, m, form), ci.record_bytes = channel_record_bytes(t);
-  ci.bytes_read = ci.bytes_written = n * elem;
+  ci.bytes_read = ci.bytes_written = n * cp.elem;
   return ARTN_OK;
 }
 
@@ -103,13 +83,9 @@ static void channel_launch(const ChannelPlan &cp, T *a, const void *table, const
   const dim3 grid((unsigned)std::min<int64_t>(cp.info.n_tiles, ARTN_WGATE_MAX_GRID)), block(ARTN_BORN_THREADS);
   const size_t lds = (size_t)cp.info.lds_bytes;
   const int m = cp.m;
-  switch (cp.t) {
-  case 1: hipLaunchKernelGGL((artn_k_channel<T, 1>), grid, block, lds, st, a, tab, rec, m); break;
-  case 2: hipLaunchKernelGGL((artn_k_channel<T, 2>), grid, block, lds, st, a, tab, rec, m); break;
-  case 3: hipLaunchKernelGGL((artn_k_channel<T, 3>), grid, block, lds, st, a, tab, rec, m); break;
-  case 4: hipLaunchKernelGGL((artn_k_channel<T, 4>), grid, block, lds, st, a, tab, rec, m); break;
-  case 5: hipLaunchKernelGGL((artn_k_channel<T, 5>), grid, block, lds, st, a, tab, rec, m); break;
-  }
+  state_with_k(cp.t, [&](auto k) {
+    hipLaunchKernelGGL((artn_k_channel<T, decltype(k)::value>), grid, block, lds, st, a, tab, rec, m);
+  });
 }
 
 static int channel_record_fits(int64_t record_bytes, int t) {
@@ -147,43 +123,20 @@ int artn_channel_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims,
   g.k = (uint64_t)t, g.tile_bits = (uint64_t)cp.tb, g.n_tiles = (uint64_t)cp.info.n_tiles, g.segment = (uint64_t)cp.info.segment;
   g.group_bits = (uint64_t)gb, g.n_high = (uint64_t)(cp.tb - cp.seg_bits);
   for (int j = cp.seg_bits; j < cp.tb; ++j) g.high_bit[j - cp.seg_bits] = (uint64_t)cp.tile[j];
-  // the swizzle of artn_wgate_pack: the window is the lowest P = min(6, gb) tile-local bits; its non-targets are group bits
-  // 0 .. P-j-1 and LDS index bits of the same number, its j targets get the LDS index bits P-j .. P-1
-  const int window = std::min(6, gb);
-  int low_targets = 0;
-  for (int p = 0; p < window; ++p)
-    if (std::find(cp.target.begin(), cp.target.end(), cp.tile[p]) != cp.target.end()) ++low_targets;
-  int rank = 0, seen = 0; // non-targets / window targets below the position
-  for (int p = 0; p < cp.tb; ++p) {
-    g.mem_col[p] = (uint64_t)1 << cp.tile[p];
-    const auto at = std::find(cp.target.begin(), cp.target.end(), cp.tile[p]);
-    if (at == cp.target.end()) {
-      g.lds_col[p] = (uint64_t)1 << rank++;
-      continue;
-    }
-    const int listed = (int)(at - cp.target.begin()), row_bit = t - 1 - listed; // the LAST listed target is row bit 0
-    g.target_bit[listed] = (uint64_t)cp.tile[p], g.target_pos[listed] = (uint64_t)p;
-    if (p < window) g.swizzle[row_bit] = (uint64_t)1 << (window - low_targets + seen++);
-    g.lds_col[p] = ((uint64_t)1 << (gb + row_bit)) ^ g.swizzle[row_bit];
-  }
+  state_tile_cols(cp, g.mem_col, g.lds_col, g.target_bit, g.target_pos, g.swizzle);
   ct.m = (uint64_t)m, ct.form = (uint64_t)form, ct.weight_doubles = (uint64_t)wd;
-  // per operator: the block mask of artn_wgate_pack, "diagonal" and "exactly the identity"
-  const int r = std::min(rows, ARTN_WGATE_ROWS), nb = rows / r;
+  // per operator: the block mask, "diagonal" and "exactly the identity"
   ArtnChannelOp *ops = (ArtnChannelOp *)((ArtnChannelTable *)table + 1);
   bool all_diagonal = true;
   for (int j = 0; j < m; ++j) {
     const double *mat = mats + ((size_t)j << (2 * t + 1));
     ArtnChannelOp op = {};
-    bool diagonal = true, identity = true;
+    op.block_mask = state_block_mask(mat, rows);
+    bool diagonal = true;
+    state_matrix_scan(mat, rows, diagonal);
+    bool identity = diagonal;
     for (int row = 0; row < rows; ++row)
-      for (int col = 0; col < rows; ++col) {
-        const double re = mat[2 * (row * rows + col)], im = mat[2 * (row * rows + col) + 1];
-        if (re != 0.0 || im != 0.0) {
-          op.block_mask |= (uint64_t)1 << ((row / r) * nb + col / r);
-          if (row != col) diagonal = false;
-        }
-        if (re != (row == col ? 1.0 : 0.0) || im != 0.0) identity = false;
-      }
+      if (mat[2 * (row * rows + row)] != 1.0 || mat[2 * (row * rows + row) + 1] != 0.0) identity = false;
     op.flags = (diagonal ? ARTN_CHANNEL_OP_DIAGONAL : 0) | (identity ? ARTN_CHANNEL_OP_IDENTITY : 0);
     ops[j] = op;
     g.block_mask |= op.block_mask;

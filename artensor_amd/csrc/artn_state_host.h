@@ -1,7 +1,7 @@
 // artn_state_host.h -- host plumbing shared by the operations on a dense amplitude array (artn_born.hip, artn_rdm.hip,
 // artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the max_rank rule and the
-// rank dispatch of the run kernels, the matrix scan, the argument checks of the pack / apply entries and the parts of a packed
-// table.  Codes and texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording
+// rank dispatch of the run kernels, the matrix scan, the argument checks of the pack / apply entries, the parts of a packed
+// table, and the plan, the column packer and the K dispatch of the tile kernels (wide gates, controlled gates, channels).  Codes and texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording
 // (`who`: "gate circuits take", ...) and its own precedence between the errors, so the pieces are separate functions.
 #pragma once
 #include <algorithm>
@@ -145,4 +145,99 @@ template <typename Header, typename Void, typename Run, typename Rec>
 static void state_table_parts(Void *table, size_t n_runs, Run *&runs, Rec *&recs) {
   runs = (Run *)((Header *)table + 1);
   recs = (Rec *)(runs + n_runs);
+}
+
+// ---- the tile kernels: artn_k_wgate, artn_k_cgate, artn_k_channel (include/artn.h: PLAN of artn_wgate_query) ----------------
+
+// One listed dimension of a gate or channel (`what`: "gates", "channels"): in range, of extent 2, not among `seen`, the
+// dimensions listed before it -- the n_targets targets first, so a control that repeats one of those gets its own text.
+static int state_tile_dim(const ArtnMarginalDesc *d, int32_t dim, const std::vector<int32_t> &seen, size_t n_targets, bool is_control,
+                          const char *what) {
+  if (dim < 0 || dim >= d->n_dims) return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " out of range");
+  if (d->extent[dim] != 2)
+    return fail(ARTN_E_INVALID, std::string(what) + " act on dimensions of extent 2; dimension " + std::to_string(dim) + " has extent " +
+                                    std::to_string(d->extent[dim]));
+  for (size_t i = 0; i < seen.size(); ++i)
+    if (seen[i] == dim) {
+      if (is_control && i < n_targets)
+        return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " is both a target and a control");
+      return fail(ARTN_E_INVALID, "the dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
+    }
+  return ARTN_OK;
+}
+// the k target dimensions dims[0 .. k-1] of a family without controls -> their memory bits, in the order listed
+static int state_tile_targets(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const char *what, std::vector<int> &target) {
+  std::vector<int32_t> seen;
+  for (int j = 0; j < k; ++j) {
+    if (int rc = state_tile_dim(d, dims[j], seen, (size_t)k, false, what)) return rc;
+    seen.push_back(dims[j]);
+    target.push_back(__builtin_ctzll((uint64_t)d->stride[dims[j]]));
+  }
+  return ARTN_OK;
+}
+
+struct TilePlan {
+  int tb = 0, seg_bits = 0;
+  std::vector<int> target; // memory bits in the order listed
+  std::vector<int> tile;   // tile bits, ascending
+  int64_t elem = 0, n_tiles = 0, segment = 0, lds_bytes = 0;
+};
+
+// The tile of a state of 2^sub_bits walked elements: the targets (set before the call) and the lowest bits that are neither
+// targets nor `excluded` (the high controls), min(TB, sub_bits) in all, ascending; seg_bits = the leading tile bits j that are
+// memory bit j.
+static void state_tile_plan(int32_t dtype, int sub_bits, uint64_t excluded, TilePlan &tp) {
+  tp.tb = std::min(dtype == ARTN_C64 ? ARTN_WGATE_TILE_BITS_C64 : ARTN_WGATE_TILE_BITS_C128, sub_bits);
+  for (int b : tp.target) excluded |= (uint64_t)1 << b;
+  tp.tile = tp.target;
+  for (int b = 0; (int)tp.tile.size() < tp.tb; ++b)
+    if (!((excluded >> b) & 1)) tp.tile.push_back(b);
+  std::sort(tp.tile.begin(), tp.tile.end());
+  tp.seg_bits = 0;
+  while (tp.seg_bits < tp.tb && tp.tile[tp.seg_bits] == tp.seg_bits) ++tp.seg_bits;
+  tp.elem = dtype == ARTN_C64 ? 8 : 16;
+  tp.n_tiles = (int64_t)1 << (sub_bits - tp.tb), tp.segment = (int64_t)1 << tp.seg_bits, tp.lds_bytes = tp.elem << tp.tb;
+}
+
+// The columns of a packed table, per tile-local bit, and the swizzle: the window is the lowest P = min(6, gb) tile-local bits; its
+// non-targets are group bits 0 .. P-j-1 and LDS index bits of the same number, its j targets get the LDS index bits P-j .. P-1.
+// The r-th non-target tile bit is group bit r: its lds_col is 1 << r.
+static void state_tile_cols(const TilePlan &tp, uint64_t *mem_col, uint64_t *lds_col, uint64_t *target_bit, uint64_t *target_pos,
+                            uint64_t *swizzle) {
+  const int k = (int)tp.target.size(), gb = tp.tb - k, window = std::min(6, gb);
+  int low_targets = 0;
+  for (int p = 0; p < window; ++p)
+    if (std::find(tp.target.begin(), tp.target.end(), tp.tile[p]) != tp.target.end()) ++low_targets;
+  int rank = 0, seen = 0; // non-targets / window targets below the position
+  for (int p = 0; p < tp.tb; ++p) {
+    mem_col[p] = (uint64_t)1 << tp.tile[p];
+    const auto at = std::find(tp.target.begin(), tp.target.end(), tp.tile[p]);
+    if (at == tp.target.end()) {
+      lds_col[p] = (uint64_t)1 << rank++;
+      continue;
+    }
+    const int listed = (int)(at - tp.target.begin()), row_bit = k - 1 - listed; // the LAST listed target is row bit 0
+    target_bit[listed] = (uint64_t)tp.tile[p], target_pos[listed] = (uint64_t)p;
+    if (p < window) swizzle[row_bit] = (uint64_t)1 << (window - low_targets + seen++);
+    lds_col[p] = ((uint64_t)1 << (gb + row_bit)) ^ swizzle[row_bit];
+  }
+}
+
+// bit rb * nb + cb: block (rb, cb) of ARTN_WGATE_ROWS x ARTN_WGATE_ROWS entries of the rows x rows matrix has a non-zero
+static uint64_t state_block_mask(const double *mat, int rows) {
+  const int r = std::min(rows, ARTN_WGATE_ROWS), nb = rows / r;
+  uint64_t mask = 0;
+  for (int row = 0; row < rows; ++row)
+    for (int col = 0; col < rows; ++col)
+      if (mat[2 * (row * rows + col)] != 0.0 || mat[2 * (row * rows + col) + 1] != 0.0) mask |= (uint64_t)1 << ((row / r) * nb + col / r);
+  return mask;
+}
+
+// f(std::integral_constant<int, K>) for the run-time k = 1 .. ARTN_WGATE_MAX_K; the plans admit no other k
+template <int K = 1, typename F>
+static void state_with_k(int k, F &&f) {
+  if constexpr (K <= ARTN_WGATE_MAX_K) {
+    if (k == K) f(std::integral_constant<int, K>());
+    else state_with_k<K + 1>(k, f);
+  }
 }

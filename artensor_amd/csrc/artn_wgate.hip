@@ -11,10 +11,8 @@
 #include "artn_state_host.h"
 #include "artn_wgate_kernel.h"
 
-struct WgatePlan {
-  int k = 0, n_bits = 0, tb = 0, seg_bits = 0;
-  std::vector<int> target;  // memory bits in the order listed
-  std::vector<int> tile;    // tile bits, ascending
+struct WgatePlan : TilePlan {
+  int k = 0, n_bits = 0;
   ArtnWgateInfo info = {};
 };
 
@@ -23,7 +21,6 @@ struct WgatePlan {
 static int wgate_plan(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const double *mat, WgatePlan &wp) {
   if (int rc = state_desc(d, "wide gates take", ARTN_MARG_MAX_DIMS, false)) return rc;
   if (!dims) return fail(ARTN_E_INVALID, "null pointer");
-  const int nd = d->n_dims;
   StateLayout l;
   if (int rc = state_layout(d, l)) return rc;
   if (int rc = state_bits_only(l, "wide gates take")) return rc;
@@ -35,32 +32,14 @@ static int wgate_plan(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims,
     return fail(ARTN_E_INVALID, "a gate on " + std::to_string(k) + " dimensions needs a state of at least 2^" + std::to_string(k) +
                                     " elements; this one has " + std::to_string((long long)n));
   wp.k = k, wp.n_bits = n_bits;
-  for (int j = 0; j < k; ++j) {
-    const int32_t dim = dims[j];
-    if (dim < 0 || dim >= nd) return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " out of range");
-    if (d->extent[dim] != 2)
-      return fail(ARTN_E_INVALID, "gates act on dimensions of extent 2; dimension " + std::to_string(dim) + " has extent " +
-                                      std::to_string(d->extent[dim]));
-    for (int i = 0; i < j; ++i)
-      if (dims[i] == dim) return fail(ARTN_E_INVALID, "the dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
-    wp.target.push_back(__builtin_ctzll((uint64_t)d->stride[dim]));
-  }
+  if (int rc = state_tile_targets(d, k, dims, "gates", wp.target)) return rc;
   bool diagonal = false;
   if (mat && !state_matrix_scan(mat, 1 << k, diagonal)) return fail(ARTN_E_INVALID, "a matrix entry is not finite");
-  const int tb_max = d->dtype == ARTN_C64 ? ARTN_WGATE_TILE_BITS_C64 : ARTN_WGATE_TILE_BITS_C128;
-  wp.tb = std::min(tb_max, n_bits);
-  wp.tile = wp.target;
-  for (int b = 0; (int)wp.tile.size() < wp.tb; ++b)
-    if (std::find(wp.target.begin(), wp.target.end(), b) == wp.target.end()) wp.tile.push_back(b);
-  std::sort(wp.tile.begin(), wp.tile.end());
-  wp.seg_bits = 0;
-  while (wp.seg_bits < wp.tb && wp.tile[wp.seg_bits] == wp.seg_bits) ++wp.seg_bits;
-  const int64_t elem = d->dtype == ARTN_C64 ? 8 : 16;
+  state_tile_plan(d->dtype, n_bits, 0, wp);
   wp.info.k = k, wp.info.tile_bits = wp.tb, wp.info.diagonal = diagonal ? 1 : 0;
-  wp.info.n_tiles = n >> wp.tb, wp.info.segment = (int64_t)1 << wp.seg_bits;
-  wp.info.lds_bytes = elem << wp.tb;
+  wp.info.n_tiles = wp.n_tiles, wp.info.segment = wp.segment, wp.info.lds_bytes = wp.lds_bytes;
   wp.info.table_bytes = (int64_t)sizeof(ArtnWgateTable) + ((int64_t)16 << (2 * k));
-  wp.info.bytes_read = wp.info.bytes_written = n * elem;
+  wp.info.bytes_read = wp.info.bytes_written = n * wp.elem;
   return ARTN_OK;
 }
 
@@ -69,13 +48,7 @@ static void wgate_launch(const WgatePlan &wp, T *a, const void *table, hipStream
   const ArtnWgateTable *tab = (const ArtnWgateTable *)table;
   const dim3 grid((unsigned)std::min<int64_t>(wp.info.n_tiles, ARTN_WGATE_MAX_GRID)), block(ARTN_BORN_THREADS);
   const size_t lds = (size_t)wp.info.lds_bytes;
-  switch (wp.k) {
-  case 1: hipLaunchKernelGGL((artn_k_wgate<T, 1>), grid, block, lds, st, a, tab); break;
-  case 2: hipLaunchKernelGGL((artn_k_wgate<T, 2>), grid, block, lds, st, a, tab); break;
-  case 3: hipLaunchKernelGGL((artn_k_wgate<T, 3>), grid, block, lds, st, a, tab); break;
-  case 4: hipLaunchKernelGGL((artn_k_wgate<T, 4>), grid, block, lds, st, a, tab); break;
-  case 5: hipLaunchKernelGGL((artn_k_wgate<T, 5>), grid, block, lds, st, a, tab); break;
-  }
+  state_with_k(wp.k, [&](auto k) { hipLaunchKernelGGL((artn_k_wgate<T, decltype(k)::value>), grid, block, lds, st, a, tab); });
 }
 
 extern "C" {
@@ -104,30 +77,8 @@ int artn_wgate_pack(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, c
   t.k = (uint64_t)k, t.tile_bits = (uint64_t)wp.tb, t.n_tiles = (uint64_t)wp.info.n_tiles, t.segment = (uint64_t)wp.info.segment;
   t.flags = wp.info.diagonal ? ARTN_GATE_DIAGONAL : 0, t.group_bits = (uint64_t)gb, t.n_high = (uint64_t)(wp.tb - wp.seg_bits);
   for (int j = wp.seg_bits; j < wp.tb; ++j) t.high_bit[j - wp.seg_bits] = (uint64_t)wp.tile[j]; // (all targets: include/artn.h)
-  // the swizzle: the window is the lowest P = min(6, gb) tile-local bits; its non-targets are group bits 0 .. P-j-1 and LDS
-  // index bits of the same number, its j targets get the LDS index bits P-j .. P-1
-  const int window = std::min(6, gb);
-  int low_targets = 0;
-  for (int p = 0; p < window; ++p)
-    if (std::find(wp.target.begin(), wp.target.end(), wp.tile[p]) != wp.target.end()) ++low_targets;
-  int rank = 0, seen = 0; // non-targets / window targets below the position
-  for (int p = 0; p < wp.tb; ++p) {
-    t.mem_col[p] = (uint64_t)1 << wp.tile[p];
-    const auto at = std::find(wp.target.begin(), wp.target.end(), wp.tile[p]);
-    if (at == wp.target.end()) {
-      t.lds_col[p] = (uint64_t)1 << rank++;
-      continue;
-    }
-    const int listed = (int)(at - wp.target.begin()), row_bit = k - 1 - listed; // the LAST listed target is row bit 0
-    t.target_bit[listed] = (uint64_t)wp.tile[p], t.target_pos[listed] = (uint64_t)p;
-    if (p < window) t.swizzle[row_bit] = (uint64_t)1 << (window - low_targets + seen++);
-    t.lds_col[p] = ((uint64_t)1 << (gb + row_bit)) ^ t.swizzle[row_bit];
-  }
-  const int r = std::min(rows, ARTN_WGATE_ROWS), nb = rows / r;
-  for (int row = 0; row < rows; ++row)
-    for (int col = 0; col < rows; ++col)
-      if (mat[2 * (row * rows + col)] != 0.0 || mat[2 * (row * rows + col) + 1] != 0.0)
-        t.block_mask |= (uint64_t)1 << ((row / r) * nb + col / r);
+  state_tile_cols(wp, t.mem_col, t.lds_col, t.target_bit, t.target_pos, t.swizzle);
+  t.block_mask = state_block_mask(mat, rows);
   *(ArtnWgateTable *)table = t;
   std::copy(mat, mat + 2 * rows * rows, (double *)((ArtnWgateTable *)table + 1));
   return ARTN_OK;

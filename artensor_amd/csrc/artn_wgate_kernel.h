@@ -26,6 +26,18 @@
 // tile-local bits an LDS index bit of its own below bit 6, so those accesses spread over the banks as well.
 //
 // Arithmetic: gates_term of artn_gates_kernel.h adds every term; accumulators start at -0.0; one rounding per component to T.
+//
+// artn_k_cgate (artn_cgate_kernel.h) and artn_k_channel (artn_channel_kernel.h) repeat this tile loop, and all three still write
+// it out: the rule of artn_block_kernel.h (a function is what compiles to the instructions of the text it replaces) admitted no
+// cut.  Tried on all 30 instantiations, compared with tools/compare_device_code.py (profiles/tile_kernel_device_code.md):
+//   - the whole loop as one __forceinline__ function template over the table type, with a walk policy (tile base, live item, a
+//     compile-time MASKED for cgate's branch): no instantiation keeps its text; VGPRs move by -8 .. +2 (K = 3: 132 -> 134,
+//     156 -> 150).  The same with the function's table parameter __restrict__: +34 .. +42 VGPRs everywhere (98 -> 132).
+//     Even the unchanged kernel body moved into a function differs, so the boundary itself is the cause: the kernel argument's
+//     noalias is not known inside the callee when it is simplified before inlining.
+//   - phases 1 and 4 alone as functions (table, base, mt, vt passed in): 241 .. 280 VGPRs and 32 AGPRs, from 98 .. 156.
+//   - wgate_thread_cols for mt and vt: two loops of branches in place of one, other text.
+// The host half has no such constraint and is shared: artn_state_host.h.
 #ifndef ARTN_WGATE_KERNEL_H
 #define ARTN_WGATE_KERNEL_H
 

@@ -19,7 +19,9 @@ from artensor_amd import controlled as CG
 from test_gates_cpu import random_unitary
 from test_pauli_apply_cpu import contiguous_strides, desc, ptr
 from test_wide_gates_cpu import pack as wide_pack
-from test_wide_gates_cpu import random_layout, xor_cols
+from test_wide_gates_cpu import random_layout
+from tile_table import cgate_fields as decode
+from tile_table import follow_columns, insert_holes, xor_cols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED, NODEVICE = -1, -2, -4
@@ -279,24 +281,6 @@ def pack(shape, strides, m, targets, controls, values, dtype):
     return CG._cgate_pack(CG._desc(shape, strides, dtype), t, targets, c, controls, values, mat)
 
 
-def decode(table):
-    w = table.view(np.uint64)
-    names = ["t", "tile_bits", "n_tiles", "segment", "flags", "group_bits", "segment_bits", "block_mask", "n_holes", "high_want",
-             "high_mask", "group_mask", "group_want"]
-    head = {k: int(v) for k, v in zip(names, w[:13])}
-    arrays = {"target_bit": w[13:18], "target_pos": w[18:23], "swizzle": w[23:28], "mem_col": w[28:44], "lds_col": w[44:60],
-              "hole_bit": w[60:124]}
-    assert int(w[124]) == 0
-    return head, {k: v.astype(np.int64) for k, v in arrays.items()}
-
-
-def insert_holes(q, holes):
-    for p in holes:
-        p = int(p)
-        q = ((q >> p) << (p + 1)) | (q & ((1 << p) - 1))
-    return q
-
-
 @pytest.mark.parametrize("dtype", [torch.complex64, torch.complex128])
 def test_the_packed_table_followed_as_the_kernel_follows_it(dtype):
     for n_bits, shape, strides, (m, targets, controls, values) in layouts_and_gates():
@@ -314,20 +298,12 @@ def test_the_packed_table_followed_as_the_kernel_follows_it(dtype):
         low_want = sum(v << b for b, v in zip(cbits, values) if b < LB[dtype])
         assert head["high_mask"] == high_mask and head["high_want"] == high_want
         mem_col, lds_col, swizzle = arr["mem_col"], arr["lds_col"], arr["swizzle"]
-        assert tuple(arr["target_bit"][:t]) == tbits and all(mem_col[arr["target_pos"][j]] == 1 << tbits[j] for j in range(t))
-        assert not mem_col[tb:].any() and not lds_col[tb:].any() and not swizzle[t:].any() and all(int(s) < 2 ** gb for s in swizzle)
         holes = arr["hole_bit"][:head["n_holes"]]
         assert list(holes) == sorted(set(int(h) for h in holes)) and not arr["hole_bit"][head["n_holes"]:].any()
         tile_bits = [int(c).bit_length() - 1 for c in mem_col[:tb]]
         s = head["segment_bits"]
         assert set(int(h) for h in holes) == set(tile_bits[s:]) | {b for b in cbits if b >= LB[dtype]}
-        u = np.arange(2 ** tb, dtype=np.int64)
-        mem, lds = xor_cols(u, mem_col), xor_cols(u, lds_col)
-        assert np.array_equal(mem[:2 ** s], u[:2 ** s])                      # a segment is contiguous, and the first one starts the tile
-        assert np.array_equal(np.sort(lds), u)                              # the LDS image is a bijection: nothing outside 2^tb
-        w = min(6, gb)
-        for start in range(0, 2 ** tb, max(2 ** w, 2 ** tb // 8)):          # the banks, as for the wide gate
-            assert np.array_equal(np.sort(lds[start:start + 2 ** w] & (2 ** w - 1)), u[:2 ** w])
+        mem, off, rest = follow_columns(tb, t, s, tbits, arr["target_bit"], arr["target_pos"], swizzle, mem_col, lds_col)
         # the walk: exactly the elements whose high control bits are the wanted ones, each once, all inside the state
         base = insert_holes(np.arange(info.n_tiles, dtype=np.int64) << s, holes) | high_want
         every = (base[:, None] | mem[None, :]).reshape(-1)
@@ -335,18 +311,6 @@ def test_the_packed_table_followed_as_the_kernel_follows_it(dtype):
         assert every.min() >= 0 and every.max() < n
         index = np.arange(n, dtype=np.int64)
         assert np.array_equal(np.sort(every), index[(index & high_mask) == high_want])
-        # (row c, group g) -> LDS index, as phases 2 and 3 form it
-        c_, g_ = np.meshgrid(np.arange(2 ** t), np.arange(2 ** gb), indexing="ij")
-        idx = ((c_ << gb) | g_) ^ xor_cols(c_, swizzle[:t])
-        assert np.array_equal(np.sort(idx.reshape(-1)), u)
-        where = np.empty(2 ** tb, dtype=np.int64)
-        where[lds] = mem
-        off = where[idx]                                                   # [row, group]: memory offset inside the tile
-        row_of = sum(((off >> tbits[t - 1 - i]) & 1) << i for i in range(t))
-        assert np.array_equal(row_of, c_)                                  # the LAST listed target is row bit 0
-        rest = off & ~sum(1 << b for b in tbits)
-        assert (rest == rest[0:1]).all() and len(set(rest[0])) == 2 ** gb   # a group differs in the target bits only
-        assert np.array_equal(np.argsort(rest[0]), np.arange(2 ** gb))
         # the group mask passes exactly the groups whose low control bits are right
         g = np.arange(2 ** gb, dtype=np.int64)
         passes = (g & head["group_mask"]) == head["group_want"]

@@ -18,6 +18,7 @@ from artensor_amd.fixtures import load_case
 from test_gates_cpu import dense_unitary, n12_gates, numpy_gate, random_unitary
 from test_gpu_parity import amp_rel
 from test_pauli_apply_cpu import contiguous_strides, desc, ptr
+from tile_table import follow_columns, insert_holes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -185,13 +186,6 @@ def pack(shape, strides, m, dims, dtype):
     return WG._wgate_pack(WG._desc(shape, strides, dtype), k, dims, mat)
 
 
-def xor_cols(index, cols):
-    out = np.zeros_like(index)
-    for b, col in enumerate(cols):
-        out ^= ((index >> b) & 1) * int(col)
-    return out
-
-
 @pytest.mark.parametrize("dtype", [torch.complex64, torch.complex128])
 def test_the_packed_table_followed_as_the_kernel_follows_it(dtype):
     """Every index the kernel forms from the table, in numpy: phases 1 and 4 (tile-local index -> memory offset and LDS index)
@@ -207,36 +201,13 @@ def test_the_packed_table_followed_as_the_kernel_follows_it(dtype):
         assert head[:4] == [k, tb, info.n_tiles, info.segment] and head[4] == 0 and head[5] == gb
         assert table.nbytes == info.table_bytes == 480 + 16 * 4 ** k
         want = tuple(int(strides[d]).bit_length() - 1 for d in dims)
-        assert tuple(target_bit[:k]) == want and all(mem_col[target_pos[j]] == 1 << want[j] for j in range(k))
-        assert not mem_col[tb:].any() and not lds_col[tb:].any() and not swizzle[k:].any() and all(int(s) < 2 ** gb for s in swizzle)
         seg_bits = tb - n_high
         assert 2 ** seg_bits == info.segment and sorted(high_bit[:n_high]) == list(high_bit[:n_high]) and set(high_bit[:n_high]) <= set(want)
-        u = np.arange(2 ** tb, dtype=np.int64)
-        mem, lds = xor_cols(u, mem_col), xor_cols(u, lds_col)
-        assert np.array_equal(mem[:2 ** seg_bits], u[:2 ** seg_bits])       # a segment is contiguous, and the first one starts the tile
-        assert np.array_equal(np.sort(lds), u)                              # the image is a bijection: nothing outside 2^tb
-        # the low window: 64 consecutive tile-local indices take 64 different values of the low six LDS index bits (the banks)
-        w = min(6, gb)
-        for start in range(0, 2 ** tb, max(2 ** w, 2 ** tb // 8)):
-            assert np.array_equal(np.sort(lds[start:start + 2 ** w] & (2 ** w - 1)), u[:2 ** w])
+        mem, _, _ = follow_columns(tb, k, seg_bits, want, target_bit, target_pos, swizzle, mem_col, lds_col)
         # tiles: every element of the state exactly once
-        q = np.arange(info.n_tiles, dtype=np.int64) << seg_bits
-        for p in high_bit[:n_high]:
-            q = ((q >> p) << (p + 1)) | (q & ((1 << int(p)) - 1))
+        q = insert_holes(np.arange(info.n_tiles, dtype=np.int64) << seg_bits, high_bit[:n_high])
         every = (q[:, None] | mem[None, :]).reshape(-1)
         assert every.min() == 0 and every.max() == n - 1 and np.array_equal(np.sort(every), np.arange(n))
-        # (row c, group g) -> LDS index, as phases 2 and 3 form it; row bit i is the i-th target from the LAST listed one
-        c, g = np.meshgrid(np.arange(2 ** k), np.arange(2 ** gb), indexing="ij")
-        idx = ((c << gb) | g) ^ xor_cols(c, swizzle[:k])
-        assert np.array_equal(np.sort(idx.reshape(-1)), u)
-        where = np.empty(2 ** tb, dtype=np.int64)
-        where[lds] = mem                                                   # LDS index -> memory offset inside the tile
-        off = where[idx]                                                   # [row, group]
-        row_of = sum(((off >> want[k - 1 - i]) & 1) << i for i in range(k))
-        assert np.array_equal(row_of, c)
-        rest = off & ~sum(1 << b for b in want)
-        assert (rest == rest[0:1]).all() and len(set(rest[0])) == 2 ** gb   # a group differs in the target bits only
-        assert np.array_equal(np.argsort(rest[0]), np.arange(2 ** gb))     # consecutive groups: ascending memory order
         # the matrix, row-major (Re, Im), and the mask of its non-zero 8 x 8 blocks
         mat = table[480:].view(np.float64).reshape(2 ** k, 2 ** k, 2)
         assert np.array_equal(mat[..., 0] + 1j * mat[..., 1], m)
