@@ -18,8 +18,9 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked, norm2, overlap
-from .pauli import PauliCircuit, PauliSumOperator, _desc, _max_rank, _ptr, _split_steps
+from ._state import _Prebuilt, _checked, _desc, _dtype_code, _max_rank, _overlaps, _packed, _ptr
+from .born import norm2, overlap
+from .pauli import PauliCircuit, PauliSumOperator, _split_steps
 
 __all__ = ["pauli_adjoint_info", "PauliPairCircuit", "pauli_evolve_pair_", "adjoint_gradient"]
 
@@ -56,8 +57,7 @@ def pauli_adjoint_info(shape, strides, steps, dtype=torch.complex64, measure=Non
     default and the maximum lie one below the single-state ones).  The per-step and per-run lists of pauli_evolve_info, `measure`,
     n_measured, n_runs, n_launches = n_runs + 1 (the finish), table_bytes, workspace_bytes and bytes_read = bytes_written =
     2 * n_runs * bytes of a state."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"pauli_adjoint_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "pauli_adjoint_info")
     coeff, ops = _split_steps(steps, len(shape))
     flags = _flags(measure, ops.shape[0])
     info, xm, zm, ny, run, slot, rank, basis, pivot = _adjoint_query(_desc(shape, strides, dtype), ops, coeff, flags,
@@ -74,7 +74,7 @@ def pauli_adjoint_info(shape, strides, steps, dtype=torch.complex64, measure=Non
             "bytes_written": info.bytes_written}
 
 
-class PauliPairCircuit:
+class PauliPairCircuit(_Prebuilt):
     """The steps of a PauliCircuit for TWO tensors of one layout: validates, cuts the runs, packs the table and copies it to
     `device` once; the workspace is allocated per call, so an instance holds no state that two calls share.  circ(lam, phi,
     device=False) updates both IN PLACE (one launch per run and a finish launch) and returns t[k] = <lam| P_k |phi> taken
@@ -82,36 +82,24 @@ class PauliPairCircuit:
     tensor [K, 2] without a host synchronisation."""
 
     def __init__(self, shape, strides, dtype, steps, device, measure=None, max_rank=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"PauliPairCircuit: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"PauliPairCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU "
-                               "fallback")
+        self._bind(shape, strides, dtype, device)
         coeff, self._ops = _split_steps(steps, len(self.shape))
         flags = _flags(measure, self._ops.shape[0])
         self._d = _desc(self.shape, self.strides, dtype)
         self._max_rank = _max_rank(max_rank)
-        info = _adjoint_query(self._d, self._ops, coeff, flags, self._max_rank)[0]
-        table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-        _native.check(_native.lib().artn_pauli_adjoint_pack(ctypes.byref(self._d), _ptr(self._ops), _ptr(coeff), _ptr(flags),
-                                                            self._ops.shape[0], self._max_rank, _ptr(table), info.table_bytes))
+        table, info = _packed(_adjoint_query(self._d, self._ops, coeff, flags, self._max_rank)[0],
+                              lambda *table: _native.lib().artn_pauli_adjoint_pack(ctypes.byref(self._d), _ptr(self._ops), _ptr(coeff),
+                                                                                   _ptr(flags), self._ops.shape[0], self._max_rank,
+                                                                                   *table))
         self.n_steps, self.n_runs, self.max_rank = self._ops.shape[0], info.n_runs, info.max_rank
         self.table_bytes, self.workspace_bytes = info.table_bytes, info.workspace_bytes
-        self._table = torch.from_numpy(table.view(np.uint8)).to(self.device)
+        self._upload(table)
 
     def __call__(self, lam, phi, device=False):
         what = "adjoint.PauliPairCircuit"
         for x in (lam, phi):
-            _checked(x, what)
-            if tuple(x.shape) != self.shape or tuple(x.stride()) != self.strides or x.dtype != self.dtype:
-                raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                                 f"{tuple(x.shape)}, {tuple(x.stride())}, {x.dtype}")
-            if x.device != self._table.device:
-                raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {x.device}")
-        nbytes = phi.numel() * phi.element_size()
-        if lam.data_ptr() < phi.data_ptr() + nbytes and phi.data_ptr() < lam.data_ptr() + nbytes:
+            self._check(x, what)
+        if _overlaps(lam, phi):
             raise ValueError(f"{what}: lam overlaps phi")
         out = torch.empty((self.n_steps, 2), dtype=torch.float64, device=phi.device)
         ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)   # (per call: calls may overlap on streams)

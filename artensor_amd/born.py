@@ -13,35 +13,10 @@ import ctypes
 import torch
 
 from . import _native
+from ._state import _DTYPES, _checked, _dense_layout
 
 __all__ = ["born_plan", "overlap", "norm2", "fidelity", "block_sums", "marginal_info", "marginal_probabilities", "sample",
            "linear_xeb", "memory_to_multi_index"]
-
-_DTYPES = {torch.complex64: _native.ARTN_C64, torch.complex128: _native.ARTN_C128}
-
-
-def _dense_layout(shape, strides):
-    """Number of elements of a dense layout; ValueError when the strides are not a permutation of a contiguous layout."""
-    n = 1
-    for e, s in sorted(((int(e), int(s)) for e, s in zip(shape, strides) if e != 1), key=lambda p: p[1]):
-        if e < 1:
-            raise ValueError("Born statistics of an empty tensor are undefined")
-        if s != n:
-            raise ValueError(f"the tensor is not dense (shape {tuple(shape)}, strides {tuple(strides)}): its strides are not a "
-                             "permutation of a contiguous layout -- pass amps.contiguous()")
-        n *= e
-    return n
-
-
-def _checked(t, what):
-    _native.require_gpu(t, what)
-    if t.dtype not in _DTYPES:
-        raise TypeError(f"{what}: complex64 or complex128 amplitudes expected, got {t.dtype}")
-    n = _dense_layout(t.shape, t.stride())
-    if t.data_ptr() % 16:
-        raise ValueError(f"{what}: the tensor's memory must start on a 16-byte boundary (this view starts at an odd element "
-                         "of its storage) -- pass amps.contiguous().clone()")
-    return n
 
 
 def memory_to_multi_index(mem_index, shape, strides):

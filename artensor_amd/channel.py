@@ -34,11 +34,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked, marginal_probabilities
-from .measure import _checked_uniform, _device_uniform
-from .pauli import _desc, _ptr
+from ._state import (_Prebuilt, _checked, _checked_uniform, _desc, _device_uniform, _dims, _dtype_code, _interleaved, _lib, _packed,
+                     _ptr)
+from .born import marginal_probabilities
 from .rdm import reduced_density_matrix
-from .wide_gates import _dims
 
 __all__ = ["Channel", "ChannelOp", "channel_", "channel_step_", "channel_info", "depolarizing", "pauli_channel", "bit_flip",
            "phase_flip", "amplitude_damping", "phase_damping"]
@@ -186,15 +185,7 @@ def phase_damping(lam):
     return Channel.from_kraus([[[1, 0], [0, math.sqrt(1.0 - g)]], [[0, 0], [0, math.sqrt(g)]]], check=False)
 
 
-def _lib(what):
-    if not _native.has("artn_channel_apply"):
-        raise RuntimeError(f"{what}: the loaded library has no channel kernels -- rebuild it with `make`")
-    return _native.lib()
-
-
-def _interleaved(z):
-    z = np.ascontiguousarray(z, dtype=np.complex128)
-    return z.view(np.float64).reshape(-1).copy()
+_KERNELS = ("artn_channel_apply", "channel kernels")            # what _lib looks for, and what it calls them
 
 
 def _split(ch, dims, n_dims, what):
@@ -210,9 +201,9 @@ def _split(ch, dims, n_dims, what):
 def _query(d, ch, dims, mats, arrays=False):
     info = _native.ArtnChannelInfo()
     target, tile = np.full(_native.WGATE_MAX_K, -1, dtype=np.int32), np.full(12, -1, dtype=np.int32)
-    _native.check(_lib("channel").artn_channel_query(ctypes.byref(d), ch.t, _ptr(dims), ch.m, ch.form_code, _ptr(mats),
-                                                     ctypes.byref(info), _ptr(target) if arrays else None,
-                                                     _ptr(tile) if arrays else None))
+    _native.check(_lib(*_KERNELS, "channel").artn_channel_query(ctypes.byref(d), ch.t, _ptr(dims), ch.m, ch.form_code, _ptr(mats),
+                                                                ctypes.byref(info), _ptr(target) if arrays else None,
+                                                                _ptr(tile) if arrays else None))
     return info, target, tile
 
 
@@ -221,8 +212,7 @@ def channel_info(shape, strides, ch, dims, dtype=torch.complex64):
     (ascending), tb, n_tiles, segment, lds_bytes, table_bytes, record_bytes, reduction (what the draw reads: None, "marginal" or
     "rdm"), launches (choose + pass; the reduction's launches come on top), launches_by_form, and the nominal bytes of the pass
     (nothing is read or written where an exact identity or nothing is drawn)."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"channel_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "channel_info")
     dims, mats, _ = _split(ch, dims, len(shape), "channel_info")
     info, target, tile = _query(_desc(shape, strides, dtype), ch, dims, mats, arrays=True)
     reductions = (None, "marginal", "rdm")
@@ -237,31 +227,27 @@ def channel_info(shape, strides, ch, dims, dtype=torch.complex64):
 
 def _pack(d, ch, dims, mats, weights):
     """The channel's table (include/artn.h) as a uint8 numpy array."""
-    info = _query(d, ch, dims, mats)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_lib("channel").artn_channel_pack(ctypes.byref(d), ch.t, _ptr(dims), ch.m, ch.form_code, _ptr(mats),
-                                                    _ptr(weights), _ptr(table), info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_query(d, ch, dims, mats)[0],
+                   lambda *table: _lib(*_KERNELS, "channel").artn_channel_pack(ctypes.byref(d), ch.t, _ptr(dims), ch.m, ch.form_code,
+                                                                               _ptr(mats), _ptr(weights), *table))
 
 
-class ChannelOp:
+class ChannelOp(_Prebuilt):
     """One channel on `dims` for tensors of one layout.  Validates, plans, packs the table and copies it to `device` once;
     op(amps, uniform=None, generator=None, renormalize=True, device=False) then performs one trajectory step on amps IN PLACE and
     returns (j, p) as channel_ does; op.step(amps, ...) returns the step's record instead."""
 
     def __init__(self, shape, strides, dtype, ch, dims, device):
-        if dtype not in _DTYPES:
-            raise TypeError(f"ChannelOp: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"ChannelOp: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, device)
         self._dims, mats, weights = _split(ch, dims, len(self.shape), "ChannelOp")
         self.channel, self.t, self.m, self.form = ch, ch.t, ch.m, ch.form
         self.dims = tuple(int(x) for x in self._dims)
         self._d = _desc(self.shape, self.strides, dtype)
         table, info = _pack(self._d, ch, self._dims, mats, weights)
         self.table_bytes, self.record_bytes, self.tile_bits, self.n_tiles = info.table_bytes, info.record_bytes, info.tile_bits, info.n_tiles
+        self._upload(table)
+
+    def _upload(self, table):
         # (pinned and non-blocking: a pageable copy would make the host wait for the stream, and channel_ builds a ChannelOp per call)
         self._table = torch.from_numpy(table).pin_memory().to(self.device, non_blocking=True)
 
@@ -271,13 +257,8 @@ class ChannelOp:
         current matrix K_j * scale as (Re, Im) pairs, row-major."""
         what = "channel.ChannelOp"
         _checked_uniform(uniform, what)
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
-        dev, lib = amps.device, _lib(what)
+        self._check(amps, what)
+        dev, lib = amps.device, _lib(*_KERNELS, what)
         src = None
         if self.form == "DIAGONAL":
             src = marginal_probabilities(amps, self.dims)

@@ -20,12 +20,12 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked
+from ._state import _Prebuilt, _checked, _desc, _dims, _dtype_code, _interleaved, _lib, _packed, _ptr
 from .gates import _matrix
-from .pauli import _desc, _ptr
-from .wide_gates import _dims
 
 __all__ = ["apply_controlled_gate_", "ControlledGate", "controlled_gate_info", "mcx_", "mcz_", "mcphase_", "when", "Condition"]
+
+_KERNELS = ("artn_cgate_apply", "controlled-gate kernels")     # what _lib looks for, and what it calls them
 
 
 class Condition:
@@ -104,24 +104,15 @@ def _split(matrix, targets, controls, control_values, n_dims, what):
         controls = np.zeros(1, dtype=np.int32)
     if not 1 <= t <= _native.WGATE_MAX_K:
         return t, (targets if t else np.zeros(1, dtype=np.int32)), c, controls, values, np.zeros(2, dtype=np.float64)
-    m = _matrix(matrix, t, what)
-    mat = np.zeros(2 * m.size, dtype=np.float64)
-    mat[0::2], mat[1::2] = m.real.reshape(-1), m.imag.reshape(-1)
-    return t, targets, c, controls, values, mat
-
-
-def _lib(what):
-    if not _native.has("artn_cgate_apply"):
-        raise RuntimeError(f"{what}: the loaded library has no controlled-gate kernels -- rebuild it with `make`")
-    return _native.lib()
+    return t, targets, c, controls, values, _interleaved(_matrix(matrix, t, what))
 
 
 def _cgate_query(d, t, targets, c, controls, values, mat, arrays=False):
     info = _native.ArtnCgateInfo()
     target, control, tile = (np.full(n, -1, dtype=np.int32) for n in (_native.WGATE_MAX_K, max(c, 1), 12))
-    _native.check(_lib("controlled").artn_cgate_query(ctypes.byref(d), t, _ptr(targets), c, _ptr(controls), _ptr(values), _ptr(mat),
-                                                      ctypes.byref(info), _ptr(target) if arrays else None,
-                                                      _ptr(control) if arrays else None, _ptr(tile) if arrays else None))
+    _native.check(_lib(*_KERNELS, "controlled").artn_cgate_query(
+        ctypes.byref(d), t, _ptr(targets), c, _ptr(controls), _ptr(values), _ptr(mat), ctypes.byref(info),
+        _ptr(target) if arrays else None, _ptr(control) if arrays else None, _ptr(tile) if arrays else None))
     return info, target, control, tile
 
 
@@ -130,8 +121,7 @@ def controlled_gate_info(shape, strides, matrix, targets, controls, control_valu
     target_bits and control_bits (memory bits in the order listed), control_values, tile_bits (ascending), tb, n_selected
     (elements the gate acts on), n_tiles, segment, lds_bytes, table_bytes, bytes_read = bytes_written = the bytes of the
     elements whose high controls match, diagonal."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"controlled_gate_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "controlled_gate_info")
     t, targets, c, controls, values, mat = _split(matrix, targets, controls, control_values, len(shape), "controlled_gate_info")
     info, target, control, tile = _cgate_query(_desc(shape, strides, dtype), t, targets, c, controls, values, mat, arrays=True)
     return {"t": info.t, "c": info.c, "c_high": info.c_high, "c_low": info.c_low,
@@ -144,41 +134,29 @@ def controlled_gate_info(shape, strides, matrix, targets, controls, control_valu
 
 def _cgate_pack(d, t, targets, c, controls, values, mat):
     """The gate's table (include/artn.h) as a uint8 numpy array."""
-    info = _cgate_query(d, t, targets, c, controls, values, mat)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_lib("controlled").artn_cgate_pack(ctypes.byref(d), t, _ptr(targets), c, _ptr(controls), _ptr(values), _ptr(mat),
-                                                     _ptr(table), info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_cgate_query(d, t, targets, c, controls, values, mat)[0],
+                   lambda *table: _lib(*_KERNELS, "controlled").artn_cgate_pack(ctypes.byref(d), t, _ptr(targets), c, _ptr(controls),
+                                                                                _ptr(values), _ptr(mat), *table))
 
 
-class ControlledGate:
+class ControlledGate(_Prebuilt):
     """One controlled gate for tensors of one layout.  Validates, plans, packs the table and copies it to `device` once;
     g(amps, condition=None) then updates amps IN PLACE with one launch and returns it.  The condition belongs to the call, not
     to the table: one ControlledGate serves any condition."""
 
     def __init__(self, shape, strides, dtype, matrix, targets, controls, device, control_values=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"ControlledGate: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"ControlledGate: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, device)
         self.t, self._targets, self.c, self._controls, self._values, mat = _split(matrix, targets, controls, control_values,
                                                                                   len(self.shape), "ControlledGate")
         self._d = _desc(self.shape, self.strides, dtype)
         table, info = _cgate_pack(self._d, self.t, self._targets, self.c, self._controls, self._values, mat)
         self.table_bytes, self.tile_bits, self.n_tiles = info.table_bytes, info.tile_bits, info.n_tiles
         self.c_high, self.c_low = info.c_high, info.c_low
-        self._table = torch.from_numpy(table).to(self.device)
+        self._upload(table)
 
     def __call__(self, amps, condition=None):
         what = "controlled.ControlledGate"
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        self._check(amps, what)
         cond, mask, equals = None, 0, 0
         if condition is not None:
             if not isinstance(condition, Condition):
@@ -187,10 +165,9 @@ class ControlledGate:
                 raise ValueError(f"{what}: the condition lives on {condition.tensor.device}, the amplitudes on {amps.device}")
             cond, mask, equals = condition.tensor.data_ptr(), condition.mask, condition.equals
         with torch.cuda.device(amps.device):
-            _native.check(_lib(what).artn_cgate_apply(ctypes.byref(self._d), amps.data_ptr(), self.t, _ptr(self._targets), self.c,
-                                                      _ptr(self._controls), _ptr(self._values), self._table.data_ptr(),
-                                                      self.table_bytes, cond, mask, equals,
-                                                      _native.current_stream_ptr(amps.device)))
+            _native.check(_lib(*_KERNELS, what).artn_cgate_apply(
+                ctypes.byref(self._d), amps.data_ptr(), self.t, _ptr(self._targets), self.c, _ptr(self._controls), _ptr(self._values),
+                self._table.data_ptr(), self.table_bytes, cond, mask, equals, _native.current_stream_ptr(amps.device)))
         return amps
 
 

@@ -23,18 +23,15 @@ import numpy as np
 import torch
 
 from . import _native
+from ._state import _Prebuilt, _checked, _desc, _dtype_code, _lib, _overlaps, _packed, _ptr
 from .adjoint import PauliPairCircuit
-from .born import _DTYPES, _checked, norm2, overlap
-from .pauli import PauliCircuit, _desc, _ptr, pauli_ops
+from .born import norm2, overlap
+from .pauli import PauliCircuit, pauli_ops
 
 __all__ = ["DiagonalOperator", "diagonal_evolve_", "diagonal_expectation", "diagonal_values", "diagonal_info", "ising_terms",
            "maxcut_terms", "qaoa_gradient"]
 
-
-def _lib(what):
-    if not _native.has("artn_diag_apply"):
-        raise RuntimeError(f"{what}: the loaded library has no diagonal-operator kernels -- rebuild it with `make`")
-    return _native.lib()
+_KERNELS = ("artn_diag_apply", "diagonal-operator kernels")    # what _lib looks for, and what it calls them
 
 
 def _split(terms, n_dims, what):
@@ -61,7 +58,7 @@ def _query(d, ops, arrays=False):
         ptrs = [_ptr(x) for x in out]
     else:
         out, ptrs = (), [None] * 5
-    _native.check(_lib("diagonal").artn_diag_query(ctypes.byref(d), _ptr(ops), n, ctypes.byref(info), *ptrs))
+    _native.check(_lib(*_KERNELS, "diagonal").artn_diag_query(ctypes.byref(d), _ptr(ops), n, ctypes.byref(info), *ptrs))
     return (info,) + out
 
 
@@ -69,8 +66,7 @@ def diagonal_info(shape, strides, terms, dtype=torch.complex64):
     """Host-only: the plan of a diagonal operator.  K, n_static, n_dynamic, G (n_groups), tile_bits, n_tiles, table_bytes,
     workspace_bytes, bytes_read / bytes_written per operation (VALUES, EXPECT, PHASE, MULTIPLY, PAIR) and, per term, zmask, lo
     (the mask inside a tile), hi (the mask of the tile index) and group (-1: static); group_lo per group."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"diagonal_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "diagonal_info")
     _, ops = _split(terms, len(shape), "diagonal_info")
     info, zm, lo, hi, group, group_lo = _query(_desc(shape, strides, dtype), ops, arrays=True)
     return {"K": info.n_terms, "n_static": info.n_static, "n_dynamic": info.n_dynamic, "G": info.n_groups,
@@ -84,47 +80,31 @@ def diagonal_info(shape, strides, terms, dtype=torch.complex64):
 
 def _pack(d, ops, coeff):
     """The operator's table (include/artn.h) as a uint64 numpy array, and the query's info."""
-    info = _query(d, ops)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_lib("diagonal").artn_diag_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], _ptr(table),
-                                                  info.table_bytes))
-    return table, info
+    table, info = _packed(_query(d, ops)[0], lambda *table: _lib(*_KERNELS, "diagonal").artn_diag_pack(
+        ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], *table))
+    return table.view(np.uint64), info
 
 
-class DiagonalOperator:
+class DiagonalOperator(_Prebuilt):
     """f = sum_k c_k Z-string_k for tensors of one layout: validates, plans, packs the table and copies it to `device` once.
     The workspace of the sums is allocated per call, so an instance holds no state that two calls share."""
 
     def __init__(self, shape, strides, dtype, terms, device):
-        if dtype not in _DTYPES:
-            raise TypeError(f"DiagonalOperator: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"DiagonalOperator: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU "
-                               "fallback")
+        self._bind(shape, strides, dtype, device)
         coeff, self._ops = _split(terms, len(self.shape), "DiagonalOperator")
         self._d = _desc(self.shape, self.strides, dtype)
         table, info = _pack(self._d, self._ops, coeff)
         self.n_terms, self.n_static, self.n_dynamic, self.n_groups = info.n_terms, info.n_static, info.n_dynamic, info.n_groups
         self.tile_bits, self.n_tiles = info.tile_bits, info.n_tiles
         self.table_bytes, self.workspace_bytes = info.table_bytes, info.workspace_bytes
-        self._table = torch.from_numpy(table.view(np.uint8)).to(self.device)
-
-    def _check(self, x, what):
-        _checked(x, what)
-        if tuple(x.shape) != self.shape or tuple(x.stride()) != self.strides or x.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(x.shape)}, {tuple(x.stride())}, {x.dtype}")
-        if x.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {x.device}")
+        self._upload(table.view(np.uint8))
 
     def _apply(self, amps, mode, gamma, what):
         self._check(amps, what)
         with torch.cuda.device(amps.device):
-            _native.check(_lib(what).artn_diag_apply(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_terms,
-                                                     self._table.data_ptr(), self.table_bytes, mode, float(gamma),
-                                                     _native.current_stream_ptr(amps.device)))
+            _native.check(_lib(*_KERNELS, what).artn_diag_apply(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_terms,
+                                                                self._table.data_ptr(), self.table_bytes, mode, float(gamma),
+                                                                _native.current_stream_ptr(amps.device)))
         return amps
 
     def evolve_(self, amps, gamma):
@@ -140,8 +120,9 @@ class DiagonalOperator:
         what = "diagonal.DiagonalOperator.values"
         out = torch.empty_strided(self.shape, self.strides, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _native.check(_lib(what).artn_diag_values(ctypes.byref(self._d), _ptr(self._ops), self.n_terms, self._table.data_ptr(),
-                                                      self.table_bytes, out.data_ptr(), _native.current_stream_ptr(self.device)))
+            _native.check(_lib(*_KERNELS, what).artn_diag_values(ctypes.byref(self._d), _ptr(self._ops), self.n_terms,
+                                                                 self._table.data_ptr(), self.table_bytes, out.data_ptr(),
+                                                                 _native.current_stream_ptr(self.device)))
         return out
 
     def moments(self, amps, device=False):
@@ -152,9 +133,10 @@ class DiagonalOperator:
         out = torch.empty(3, dtype=torch.float64, device=amps.device)
         ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=amps.device)   # (per call: calls may overlap on streams)
         with torch.cuda.device(amps.device):
-            _native.check(_lib(what).artn_diag_expect(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_terms,
-                                                      self._table.data_ptr(), self.table_bytes, ws.data_ptr(), self.workspace_bytes,
-                                                      out.data_ptr(), _native.current_stream_ptr(amps.device)))
+            _native.check(_lib(*_KERNELS, what).artn_diag_expect(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_terms,
+                                                                 self._table.data_ptr(), self.table_bytes, ws.data_ptr(),
+                                                                 self.workspace_bytes, out.data_ptr(),
+                                                                 _native.current_stream_ptr(amps.device)))
         return out if device else out.cpu().numpy()
 
     def expectation(self, amps, device=False):
@@ -175,17 +157,16 @@ class DiagonalOperator:
         what = "diagonal.DiagonalOperator.pair_"
         for x in (lam, phi):
             self._check(x, what)
-        nbytes = phi.numel() * phi.element_size()
-        if lam.data_ptr() < phi.data_ptr() + nbytes and phi.data_ptr() < lam.data_ptr() + nbytes:
+        if _overlaps(lam, phi):
             raise ValueError(f"{what}: lam overlaps phi")
         out = torch.empty(2, dtype=torch.float64, device=phi.device)
         ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)
         mode = _native.DIAG_PAIR_EVOLVE if evolve else _native.DIAG_PAIR_TRANSITION
         with torch.cuda.device(phi.device):
-            _native.check(_lib(what).artn_diag_pair(ctypes.byref(self._d), lam.data_ptr(), phi.data_ptr(), _ptr(self._ops),
-                                                    self.n_terms, self._table.data_ptr(), self.table_bytes, mode, float(gamma),
-                                                    ws.data_ptr(), self.workspace_bytes, out.data_ptr(),
-                                                    _native.current_stream_ptr(phi.device)))
+            _native.check(_lib(*_KERNELS, what).artn_diag_pair(ctypes.byref(self._d), lam.data_ptr(), phi.data_ptr(), _ptr(self._ops),
+                                                               self.n_terms, self._table.data_ptr(), self.table_bytes, mode, float(gamma),
+                                                               ws.data_ptr(), self.workspace_bytes, out.data_ptr(),
+                                                               _native.current_stream_ptr(phi.device)))
         if device:
             return out
         re, im = out.tolist()

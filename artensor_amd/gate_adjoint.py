@@ -20,9 +20,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked, norm2, overlap
+from ._state import _Prebuilt, _checked, _desc, _dtype_code, _interleaved, _max_rank, _overlaps, _packed, _ptr
+from .born import norm2, overlap
 from .gates import GateCircuit, _matrix, _split_gates
-from .pauli import PauliSumOperator, _desc, _max_rank, _ptr
+from .pauli import PauliSumOperator
 
 __all__ = ["gate_adjoint_info", "GatePairCircuit", "apply_gates_pair_", "gate_adjoint_gradient", "parametric_gate"]
 
@@ -41,7 +42,7 @@ def _split_measure(measure, k):
             continue
         m = _matrix(m, int(k[g]), f"measure of gate {g}")
         flags[g] = 1
-        mmat[g, 0:2 * m.size:2], mmat[g, 1:2 * m.size:2] = m.real.reshape(-1), m.imag.reshape(-1)
+        mmat[g, :2 * m.size] = _interleaved(m)
     return flags, mmat
 
 
@@ -66,8 +67,7 @@ def gate_adjoint_info(shape, strides, gates, dtype=torch.complex64, measure=None
     default and the maximum lie one below the single-state ones).  The per-gate and per-run lists of gate_circuit_info, `measure`,
     n_measured, n_runs, n_launches = n_runs + 1 (the finish), table_bytes, workspace_bytes and bytes_read = bytes_written =
     2 * n_runs * bytes of a state."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"gate_adjoint_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "gate_adjoint_info")
     k, dims, mat = _split_gates(gates, len(shape))
     flags, mmat = _split_measure(measure, k)
     info, bits, run, slot, local, rank, pivot = _pair_query(_desc(shape, strides, dtype), k, dims, mat, mmat, flags, _max_rank(max_rank),
@@ -81,7 +81,7 @@ def gate_adjoint_info(shape, strides, gates, dtype=torch.complex64, measure=None
             "workspace_bytes": info.workspace_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written}
 
 
-class GatePairCircuit:
+class GatePairCircuit(_Prebuilt):
     """The gates of a GateCircuit for TWO tensors of one layout: validates, cuts the runs, packs the table and copies it to
     `device` once; the workspace is allocated per call, so an instance holds no state that two calls share.  measure: None (no
     gate is measured) or one entry per gate, None or a matrix M of the gate's size (any matrix).  circ(lam, phi, device=False)
@@ -90,36 +90,24 @@ class GatePairCircuit:
     host synchronisation."""
 
     def __init__(self, shape, strides, dtype, gates, device, measure=None, max_rank=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"GatePairCircuit: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"GatePairCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU "
-                               "fallback")
+        self._bind(shape, strides, dtype, device)
         self._k, self._dims, mat = _split_gates(gates, len(self.shape))
         flags, mmat = _split_measure(measure, self._k)
         self._d = _desc(self.shape, self.strides, dtype)
         self._max_rank = _max_rank(max_rank)
-        info = _pair_query(self._d, self._k, self._dims, mat, mmat, flags, self._max_rank)[0]
-        table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-        _native.check(_native.lib().artn_gates_adjoint_pack(ctypes.byref(self._d), _ptr(self._k), _ptr(self._dims), _ptr(mat), _ptr(mmat),
-                                                            _ptr(flags), self._k.shape[0], self._max_rank, _ptr(table), info.table_bytes))
+        table, info = _packed(_pair_query(self._d, self._k, self._dims, mat, mmat, flags, self._max_rank)[0],
+                              lambda *table: _native.lib().artn_gates_adjoint_pack(ctypes.byref(self._d), _ptr(self._k), _ptr(self._dims),
+                                                                                   _ptr(mat), _ptr(mmat), _ptr(flags), self._k.shape[0],
+                                                                                   self._max_rank, *table))
         self.n_gates, self.n_runs, self.max_rank, self.n_measured = self._k.shape[0], info.n_runs, info.max_rank, info.n_measured
         self.table_bytes, self.workspace_bytes = info.table_bytes, info.workspace_bytes
-        self._table = torch.from_numpy(table.view(np.uint8)).to(self.device)
+        self._upload(table)
 
     def __call__(self, lam, phi, device=False):
         what = "gate_adjoint.GatePairCircuit"
         for x in (lam, phi):
-            _checked(x, what)
-            if tuple(x.shape) != self.shape or tuple(x.stride()) != self.strides or x.dtype != self.dtype:
-                raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                                 f"{tuple(x.shape)}, {tuple(x.stride())}, {x.dtype}")
-            if x.device != self._table.device:
-                raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {x.device}")
-        nbytes = phi.numel() * phi.element_size()
-        if lam.data_ptr() < phi.data_ptr() + nbytes and phi.data_ptr() < lam.data_ptr() + nbytes:
+            self._check(x, what)
+        if _overlaps(lam, phi):
             raise ValueError(f"{what}: lam overlaps phi")
         out = torch.empty((self.n_gates, 2), dtype=torch.float64, device=phi.device)
         ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)   # (per call: calls may overlap on streams)

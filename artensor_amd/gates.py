@@ -19,8 +19,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked
-from .pauli import _desc, _max_rank, _ptr
+from ._state import _Prebuilt, _checked, _desc, _dtype_code, _interleaved, _max_rank, _packed, _ptr
 
 __all__ = ["apply_gates_", "apply_gate_", "GateCircuit", "gate_circuit_info", "gates_from_bonds", "run_circuit", "merge_gates"]
 
@@ -50,7 +49,7 @@ def _split_gates(gates, n_dims):
             dims[g, j] = x + n_dims if -n_dims <= x < 0 else x
         if k[g] in (1, 2):
             m = _matrix(gate[0], int(k[g]), f"gate {g}")
-            mat[g, 0:2 * m.size:2], mat[g, 1:2 * m.size:2] = m.real.reshape(-1), m.imag.reshape(-1)
+            mat[g, :2 * m.size] = _interleaved(m)
     return k, np.ascontiguousarray(dims), mat
 
 
@@ -74,8 +73,7 @@ def gate_circuit_info(shape, strides, gates, dtype=torch.complex64, max_rank=Non
     the order listed), run, slot_mask and local (True: the gate needs no other thread -- a diagonal matrix or targets in memory
     bits 0-1).  Per run: run_rank and run_pivot (its high target bits, ascending).  n_runs = n_launches, the effective max_rank,
     table_bytes, bytes_read = bytes_written = n_runs * bytes of the state."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"gate_circuit_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "gate_circuit_info")
     k, dims, mat = _split_gates(gates, len(shape))
     info, bits, run, slot, local, rank, pivot = _gates_query(_desc(shape, strides, dtype), k, dims, mat, _max_rank(max_rank), arrays=True)
     nr = info.n_runs
@@ -88,41 +86,28 @@ def gate_circuit_info(shape, strides, gates, dtype=torch.complex64, max_rank=Non
 
 def _gates_pack(d, k, dims, mat, max_rank):
     """The circuit table (include/artn.h) as a uint8 numpy array."""
-    info = _gates_query(d, k, dims, mat, max_rank)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_native.lib().artn_gates_pack(ctypes.byref(d), _ptr(k), _ptr(dims), _ptr(mat), k.shape[0], max_rank, _ptr(table),
-                                                info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_gates_query(d, k, dims, mat, max_rank)[0],
+                   lambda *table: _native.lib().artn_gates_pack(ctypes.byref(d), _ptr(k), _ptr(dims), _ptr(mat), k.shape[0], max_rank,
+                                                                *table))
 
 
-class GateCircuit:
+class GateCircuit(_Prebuilt):
     """An ordered list of gates [(matrix, dims), ...] for tensors of one layout.  Validates, cuts the runs, packs the table and
     copies it to `device` once; circ(amps) then updates amps IN PLACE with one launch per run and returns it.  max_rank: a run
     holds blocks of up to 2^max_rank tiles of 2^10 elements in LDS (None: 64 KiB per workgroup; 0: one launch per gate with a
     target above the tile; a two-qubit gate on two such targets always gets a block of four tiles)."""
 
     def __init__(self, shape, strides, dtype, gates, device, max_rank=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"GateCircuit: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"GateCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, device)
         self._k, self._dims, mat = _split_gates(gates, len(self.shape))
         self._d = _desc(self.shape, self.strides, dtype)
         self._max_rank = _max_rank(max_rank)
         table, info = _gates_pack(self._d, self._k, self._dims, mat, self._max_rank)
         self.n_gates, self.n_runs, self.max_rank, self.table_bytes = self._k.shape[0], info.n_runs, info.max_rank, info.table_bytes
-        self._table = torch.from_numpy(table).to(self.device)
+        self._upload(table)
 
     def __call__(self, amps):
-        what = "gates.GateCircuit"
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        self._check(amps, "gates.GateCircuit")
         with torch.cuda.device(amps.device):
             _native.check(_native.lib().artn_gates_apply(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._k), _ptr(self._dims), None,
                                                          self.n_gates, self._max_rank, self._table.data_ptr(), self.table_bytes,
@@ -172,8 +157,7 @@ def gates_from_bonds(gates, n_qubits):
 def run_circuit(gates, n_qubits, dtype=torch.complex64, device="cuda", max_rank=None):
     """gates = [(matrix, dims), ...] with dim q = qubit q, applied in place to |0..0>: a contiguous tensor of shape (2,) * n_qubits
     is the only state-sized allocation."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"run_circuit: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "run_circuit")
     state = torch.zeros(2 ** int(n_qubits), dtype=dtype, device=device)
     _native.require_gpu(state, "gates.run_circuit")
     state[0] = 1

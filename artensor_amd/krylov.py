@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked, norm2
+from ._state import _DTYPES, _checked, _dense_layout, _dtype_code
+from .born import norm2
 
 __all__ = ["krylov_info", "krylov_dots", "krylov_combine_", "ritz", "expm_e1", "KrylovResult", "lanczos", "lanczos_ground_state",
            "krylov_evolve"]
@@ -41,9 +42,7 @@ def krylov_info(shape, strides, m, dtype=torch.complex64):
     """Host-only: what krylov_dots and krylov_combine_ do for m vectors of this layout -- the grid, the batch B, the streaming
     launches of each (a finish launch follows), the workspaces and the nominal bytes moved (ValueError for a layout that is not
     dense, RuntimeError where the library refuses, TypeError for a dtype that is not complex)."""
-    from .born import _dense_layout
-    if dtype not in _DTYPES:
-        raise TypeError(f"krylov_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "krylov_info")
     n = _dense_layout(shape, strides)
     i = _info(n, dtype, m)
     return {"n": n, "grid": i.grid, "batch": i.batch, "dots_launches": i.dots_launches, "combine_launches": i.combine_launches,

@@ -15,11 +15,12 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked
-from .pauli import _desc, _ptr
+from ._state import _Prebuilt, _checked, _desc, _dtype_code, _lib, _packed, _ptr
 
 __all__ = ["permute_dims_", "swap_dims_", "reverse_qubits_", "relayout_", "BitPermutation", "bit_permutation_info",
            "busiest_dims_order"]
+
+_KERNELS = ("artn_bitperm_apply", "bit-permutation kernel")    # what _lib looks for, and what it calls it
 
 
 def _fields(shape, strides, what):
@@ -77,12 +78,6 @@ def dst_bit_of_order(shape, strides, order=None):
     return dst, tuple(new_strides)
 
 
-def _lib(what):
-    if not _native.has("artn_bitperm_apply"):
-        raise RuntimeError(f"{what}: the loaded library has no bit-permutation kernel -- rebuild it with `make`")
-    return _native.lib()
-
-
 def _dst_array(dst_bit):
     dst = np.array([int(b) for b in dst_bit] or [0], dtype=np.int32)
     return dst, len(dst_bit)
@@ -105,8 +100,9 @@ def _query(d, dst, n_bits, arrays=False):
     pass_map = np.full((P, _native.BITPERM_MAX_BITS), -1, dtype=np.int32)
     tiles = np.full((P, 16), -1, dtype=np.int32)
     load, store = np.zeros((P, 16), dtype=np.uint64), np.zeros((P, 16), dtype=np.uint64)
-    _native.check(_lib("layout").artn_bitperm_query(ctypes.byref(d), _ptr(dst), n_bits, ctypes.byref(info),
-                                                    *((_ptr(x) for x in (pass_map, tiles, load, store)) if arrays else (None,) * 4)))
+    _native.check(_lib(*_KERNELS, "layout").artn_bitperm_query(
+        ctypes.byref(d), _ptr(dst), n_bits, ctypes.byref(info),
+        *((_ptr(x) for x in (pass_map, tiles, load, store)) if arrays else (None,) * 4)))
     return info, pass_map, tiles, load, store
 
 
@@ -116,8 +112,7 @@ def bit_permutation_info(shape, strides, dtype=torch.complex64, perm=None, order
     2 x state x passes), load_degree / store_degree (the worst pass), strides (of the view afterwards) and, per pass, pass_info:
     moved_mask, map (per memory bit, where the pass sends it), tile (the memory bits of the tile, ascending), tb, n_tiles, grid,
     load_degree, store_degree and the LDS columns load_col / store_col (per tile-local bit)."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"bit_permutation_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "bit_permutation_info")
     dst_list, new_strides = _resolve(shape, strides, dst_bit, perm, order, "bit_permutation_info")
     dst, n_bits = _dst_array(dst_list)
     info, pass_map, tiles, load, store = _query(_desc(shape, strides, dtype), dst, n_bits, arrays=True)
@@ -136,25 +131,18 @@ def bit_permutation_info(shape, strides, dtype=torch.complex64, perm=None, order
 
 def _pack(d, dst, n_bits):
     """The permutation's table (include/artn.h) as a uint8 numpy array."""
-    info = _query(d, dst, n_bits)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_lib("layout").artn_bitperm_pack(ctypes.byref(d), _ptr(dst), n_bits, _ptr(table), info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_query(d, dst, n_bits)[0],
+                   lambda *table: _lib(*_KERNELS, "layout").artn_bitperm_pack(ctypes.byref(d), _ptr(dst), n_bits, *table))
 
 
-class BitPermutation:
+class BitPermutation(_Prebuilt):
     """One bit permutation for tensors of one layout, given as `dst_bit`, `perm` (permute_dims_) or `order` (relayout_).
     Validates, plans, packs the table and copies it to `device` once; p(amps) then moves the elements of amps IN PLACE, one launch
     per pass on the current stream, and returns the view that holds the result: amps itself for dst_bit and perm, a new view on
     the same storage with the strides of `order` for order."""
 
     def __init__(self, shape, strides, dtype, dst_bit=None, device=None, perm=None, order=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"BitPermutation: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device("cuda" if device is None else device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"BitPermutation: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, "cuda" if device is None else device)
         if dst_bit is None and perm is None and order is None:
             raise ValueError("BitPermutation: give one of dst_bit, perm and order")
         dst_list, self.new_strides = _resolve(self.shape, self.strides, dst_bit, perm, order, "BitPermutation")
@@ -163,21 +151,18 @@ class BitPermutation:
         self._d = _desc(self.shape, self.strides, dtype)
         table, info = _pack(self._d, self._dst, self.n_bits)
         self.passes, self.table_bytes, self.bytes_moved = info.passes, info.table_bytes, info.bytes_moved
-        self._table = torch.from_numpy(table).to(self.device) if self.passes else None
+        self._table = None                                     # (the identity holds no table and issues no launch)
+        if self.passes:
+            self._upload(table)
 
     def __call__(self, amps):
         what = "layout.BitPermutation"
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if self.passes:                                        # (the identity issues no launch)
-            if amps.device != self._table.device:
-                raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        self._check(amps, what)
+        if self.passes:
             with torch.cuda.device(amps.device):
-                _native.check(_lib(what).artn_bitperm_apply(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._dst), self.n_bits,
-                                                            self._table.data_ptr(), self.table_bytes,
-                                                            _native.current_stream_ptr(amps.device)))
+                _native.check(_lib(*_KERNELS, what).artn_bitperm_apply(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._dst),
+                                                                       self.n_bits, self._table.data_ptr(), self.table_bytes,
+                                                                       _native.current_stream_ptr(amps.device)))
         if self.new_strides == self.strides:
             return amps
         return torch.as_strided(amps, self.shape, self.new_strides, amps.storage_offset())

@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked, _dense_layout, _marginal_desc, marginal_probabilities
+from ._state import _checked, _checked_uniform, _dense_layout, _device_uniform, _dtype_code, _lib
+from .born import _marginal_desc, marginal_probabilities
 from .gates import apply_gate_
 from .rdm import reduced_density_matrix
 
@@ -56,8 +57,7 @@ def _dims(shape, dims, what):
 
 
 def _plan(shape, strides, dims, dtype, what):
-    if dtype not in _DTYPES:
-        raise TypeError(f"{what}: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, what)
     dims = _dims(shape, dims, what)
     _dense_layout(shape, strides)
     d, _ = _marginal_desc(shape, strides, dims, dtype)
@@ -76,27 +76,6 @@ def measure_info(shape, strides, dims, dtype=torch.complex64):
             "record_bytes": info.record_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written}
 
 
-def _checked_uniform(uniform, what):
-    """Host-only validation of `uniform`: None, a float in [0, 1), or a float64 GPU tensor of one element (its value is not read)."""
-    if uniform is None:
-        return
-    if isinstance(uniform, torch.Tensor):
-        if uniform.dtype != torch.float64 or uniform.numel() != 1 or not uniform.is_cuda:
-            raise ValueError(f"{what}: a uniform tensor is float64, on the GPU, with one element")
-        return
-    u = float(uniform)
-    if not 0.0 <= u < 1.0:
-        raise ValueError(f"{what}: uniform must lie in [0, 1), got {u}")
-
-
-def _device_uniform(uniform, generator, device):
-    if uniform is None:
-        return torch.rand(1, dtype=torch.float64, device=device, generator=generator)
-    if isinstance(uniform, torch.Tensor):
-        return uniform.to(device).reshape(1).contiguous()
-    return torch.full((1,), float(uniform), dtype=torch.float64, device=device)   # (a fill: no host-to-device copy)
-
-
 def collapse_(amps, dims, outcome=None, uniform=None, generator=None, renormalize=True, reset=False):
     """The work of measure_ / postselect_ / reset_, enqueued on the current stream without a host synchronisation.  Returns the
     record as a float64 GPU tensor of 4: [outcome (the bits of an int64: record.view(torch.int64)[0]), probability, total,
@@ -113,8 +92,7 @@ def collapse_(amps, dims, outcome=None, uniform=None, generator=None, renormaliz
         if not 0 <= forced < 2 ** len(dims):
             raise ValueError(f"{what}: outcome {forced} of {len(dims)} measured dims (0 .. {2 ** len(dims) - 1} expected)")
     _checked(amps, what)
-    if not _native.has("artn_measure_collapse"):
-        raise RuntimeError(f"{what}: the loaded library has no measurement kernels -- rebuild it with `make`")
+    lib = _lib("artn_measure_collapse", "measurement kernels", what)
     d, dims, info = _plan(amps.shape, amps.stride(), dims, amps.dtype, what)
     dev = amps.device
     q = marginal_probabilities(amps, dims)
@@ -122,10 +100,9 @@ def collapse_(amps, dims, outcome=None, uniform=None, generator=None, renormaliz
     rec = torch.empty(_native.MEASURE_RECORD_BYTES // 8, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         stream = _native.current_stream_ptr(dev)
-        _native.check(_native.lib().artn_measure_choose(q.data_ptr(), info.dim, None if u is None else u.data_ptr(), forced,
-                                                        int(bool(renormalize)), rec.data_ptr(), stream))
-        _native.check(_native.lib().artn_measure_collapse(ctypes.byref(d), amps.data_ptr(), rec.data_ptr(), int(bool(reset)),
-                                                          stream))
+        _native.check(lib.artn_measure_choose(q.data_ptr(), info.dim, None if u is None else u.data_ptr(), forced,
+                                              int(bool(renormalize)), rec.data_ptr(), stream))
+        _native.check(lib.artn_measure_collapse(ctypes.byref(d), amps.data_ptr(), rec.data_ptr(), int(bool(reset)), stream))
     return rec
 
 

@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked, norm2, overlap
+from ._state import _Prebuilt, _checked, _desc, _dtype_code, _max_rank, _overlaps, _packed, _ptr
+from .born import norm2, overlap
 
 __all__ = ["pauli_ops", "pauli_info", "pauli_expectation", "pauli_sum_expectation", "pauli_apply_info", "PauliSumOperator",
            "pauli_sum_apply", "pauli_apply", "pauli_rotate", "pauli_sum_variance", "pauli_evolve_info", "PauliCircuit",
@@ -60,17 +61,6 @@ def pauli_ops(paulis, n_dims):
     return np.ascontiguousarray(np.stack([_one(p, int(n_dims)) for p in terms])), single
 
 
-def _desc(shape, strides, dtype):
-    nd = len(shape)
-    if nd > _native.ARTN_MAX_LABELS:
-        raise ValueError(f"at most {_native.ARTN_MAX_LABELS} dims")
-    d = _native.ArtnMarginalDesc()
-    d.dtype, d.n_dims = _DTYPES[dtype], nd
-    for pos in range(nd):                                     # the caller's dim order; keep[] is not read
-        d.extent[pos], d.stride[pos] = int(shape[pos]), int(strides[pos])
-    return d
-
-
 def _query(d, ops, masks=False):
     n_terms = ops.shape[0]
     info = _native.ArtnPauliInfo()
@@ -90,8 +80,7 @@ def pauli_info(shape, strides, paulis, dtype=torch.complex64):
     """Host-only: the memory-bit masks of every string (xmask: bits under X or Y, zmask: bits under Z or Y, n_y), the group
     (strings of equal xmask) of each, the number of groups and of passes over the amplitudes, the workspace and the bytes read
     (RuntimeError where the library refuses; TypeError for a dtype that is not complex)."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"pauli_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "pauli_info")
     ops, _ = pauli_ops(paulis, len(shape))
     info, xm, zm, ny, group = _query(_desc(shape, strides, dtype), ops, masks=True)
     return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny],
@@ -155,10 +144,6 @@ def _split_terms(terms, n_dims):
     return np.ascontiguousarray(coeff), ops
 
 
-def _ptr(x):
-    return x.ctypes.data_as(ctypes.c_void_p)
-
-
 def _apply_query(d, ops, coeff, arrays=False):
     n_terms = ops.shape[0]
     info = _native.ArtnPauliApplyInfo()
@@ -179,8 +164,7 @@ def pauli_apply_info(shape, strides, terms, dtype=torch.complex64):
     folded coefficient c_k (-i)^n_y (complex).  Per group (numbered as they first appear): group_xmask and group_pos, its position
     in the summation order of every output element; group_order lists the groups in that order.  n_xmask_hi: the partner tiles
     fetched per output tile; table_bytes; the nominal bytes_read and bytes_written; n_launches (1)."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"pauli_apply_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "pauli_apply_info")
     coeff, ops = _split_terms(terms, len(shape))
     info, xm, zm, ny, group, folded, gx, pos = _apply_query(_desc(shape, strides, dtype), ops, coeff, arrays=True)
     ng = info.n_groups
@@ -193,47 +177,33 @@ def pauli_apply_info(shape, strides, terms, dtype=torch.complex64):
 
 def _pack(d, ops, coeff):
     """The term table (include/artn.h) as a uint8 numpy array."""
-    info = _apply_query(d, ops, coeff)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_native.lib().artn_pauli_apply_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], _ptr(table), info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_apply_query(d, ops, coeff)[0],
+                   lambda *table: _native.lib().artn_pauli_apply_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], *table))
 
 
-class PauliSumOperator:
+class PauliSumOperator(_Prebuilt):
     """H = sum_k c_k P_k (terms = [(c_k, string_k), ...], complex coefficients allowed) for tensors of one layout: validates,
     packs the term table and copies it to `device` once; op(amps, out=None) is then one launch that writes H|amps> in the layout of
     amps.  `amps` is read in place and never written."""
 
     def __init__(self, shape, strides, dtype, terms, device):
-        if dtype not in _DTYPES:
-            raise TypeError(f"PauliSumOperator: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"PauliSumOperator: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU "
-                               "fallback")
+        self._bind(shape, strides, dtype, device)
         coeff, self._ops = _split_terms(terms, len(self.shape))
         self._d = _desc(self.shape, self.strides, dtype)
         table, info = _pack(self._d, self._ops, coeff)
         self.n_terms, self.n_groups, self.table_bytes = self._ops.shape[0], info.n_groups, info.table_bytes
-        self._table = torch.from_numpy(table).to(self.device)
+        self._upload(table)
 
     def __call__(self, amps, out=None):
         what = "pauli.PauliSumOperator"
-        n = _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        self._check(amps, what)
         if out is None:
             out = torch.empty_strided(self.shape, self.strides, dtype=self.dtype, device=amps.device)
         else:
             if not isinstance(out, torch.Tensor) or out.dtype != amps.dtype or out.device != amps.device \
                     or tuple(out.shape) != self.shape or tuple(out.stride()) != self.strides:
                 raise ValueError(f"{what}: out must have the shape, strides, dtype and device of amps")
-            nbytes = n * amps.element_size()
-            if out.data_ptr() < amps.data_ptr() + nbytes and amps.data_ptr() < out.data_ptr() + nbytes:
+            if _overlaps(out, amps):
                 raise ValueError(f"{what}: out overlaps amps (there is no in-place form)")
             if out.data_ptr() % 16:
                 raise ValueError(f"{what}: out must start on a 16-byte boundary")
@@ -299,10 +269,6 @@ def _split_steps(steps, n_dims):
     return np.ascontiguousarray(coeff), ops
 
 
-def _max_rank(max_rank):
-    return -1 if max_rank is None else int(max_rank)
-
-
 def _evolve_query(d, ops, coeff, max_rank, arrays=False):
     n = ops.shape[0]
     info = _native.ArtnPauliEvolveInfo()
@@ -324,8 +290,7 @@ def pauli_evolve_info(shape, strides, steps, dtype=torch.complex64, max_rank=Non
     n_y, alpha, beta (complex), run and slot_mask.  Per run: run_rank, run_basis (memory-bit masks, ascending pivots) and
     run_pivot.  n_runs = n_launches, the effective max_rank, table_bytes, bytes_read = bytes_written = n_runs * bytes of the
     state."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"pauli_evolve_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "pauli_evolve_info")
     coeff, ops = _split_steps(steps, len(shape))
     info, xm, zm, ny, run, slot, rank, basis, pivot = _evolve_query(_desc(shape, strides, dtype), ops, coeff, _max_rank(max_rank),
                                                                     arrays=True)
@@ -342,41 +307,28 @@ def pauli_evolve_info(shape, strides, steps, dtype=torch.complex64, max_rank=Non
 
 def _evolve_pack(d, ops, coeff, max_rank):
     """The circuit table (include/artn.h) as a uint8 numpy array."""
-    info = _evolve_query(d, ops, coeff, max_rank)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_native.lib().artn_pauli_evolve_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], max_rank, _ptr(table),
-                                                       info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_evolve_query(d, ops, coeff, max_rank)[0],
+                   lambda *table: _native.lib().artn_pauli_evolve_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], max_rank,
+                                                                       *table))
 
 
-class PauliCircuit:
+class PauliCircuit(_Prebuilt):
     """An ordered list of steps a <- alpha a + beta P a for tensors of one layout: steps = [(theta, string), ...] for the rotation
     exp(-i theta P) or (alpha, beta, string) for the general step.  Validates, cuts the runs, packs the table and copies it to
     `device` once; circ(amps) then updates amps IN PLACE with one launch per run and returns it.  max_rank: a run holds blocks of
     up to 2^max_rank tiles of 2^10 elements in LDS (None: 64 KiB per workgroup; 0: one launch per step with a flip above the tile)."""
 
     def __init__(self, shape, strides, dtype, steps, device, max_rank=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"PauliCircuit: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"PauliCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, device)
         coeff, self._ops = _split_steps(steps, len(self.shape))
         self._d = _desc(self.shape, self.strides, dtype)
         self._max_rank = _max_rank(max_rank)
         table, info = _evolve_pack(self._d, self._ops, coeff, self._max_rank)
         self.n_steps, self.n_runs, self.max_rank, self.table_bytes = self._ops.shape[0], info.n_runs, info.max_rank, info.table_bytes
-        self._table = torch.from_numpy(table).to(self.device)
+        self._upload(table)
 
     def __call__(self, amps):
-        what = "pauli.PauliCircuit"
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        self._check(amps, "pauli.PauliCircuit")
         with torch.cuda.device(amps.device):
             _native.check(_native.lib().artn_pauli_evolve(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_steps,
                                                           self._max_rank, self._table.data_ptr(), self.table_bytes,

@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _checked, _marginal_desc
+from ._state import _checked, _dtype_code
+from .born import _marginal_desc
 
 __all__ = ["rdm_info", "reduced_density_matrix", "purity", "renyi_entropy", "entanglement_entropy", "entropy_of", "expectation"]
 
@@ -35,8 +36,7 @@ def _query(d):
 def rdm_info(shape, strides, keep, dtype=torch.complex64):
     """Host-only: which form a reduced density matrix takes, its size D, the tile and split counts, the workspace and the
     FLOP it executes on the matrix cores (RuntimeError where the library refuses; TypeError for a dtype that is not complex)."""
-    if dtype not in (torch.complex64, torch.complex128):
-        raise TypeError(f"rdm_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "rdm_info")
     d, _ = _marginal_desc(shape, strides, keep, dtype)
     info = _query(d)
     return {"kernel": info.kernel, "panel_bits": info.panel_bits, "tiles": info.tiles, "splits": info.splits, "dim": info.dim,

@@ -18,16 +18,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .born import _DTYPES, _checked
+from ._state import _Prebuilt, _checked, _desc, _dims, _dtype_code, _interleaved, _packed, _ptr
 from .gates import GateCircuit, _matrix
-from .pauli import _desc, _ptr
 
 __all__ = ["apply_wide_gate_", "WideGate", "wide_gate_info", "FusedCircuit", "apply_circuit_", "fuse_gates"]
-
-
-def _dims(dims, n_dims):
-    dims = [int(dims)] if isinstance(dims, (int, np.integer)) else [int(x) for x in dims]
-    return np.array([x + n_dims if -n_dims <= x < 0 else x for x in dims], dtype=np.int32)
 
 
 def _split_gate(matrix, dims, n_dims, what):
@@ -36,10 +30,7 @@ def _split_gate(matrix, dims, n_dims, what):
     k = int(dims.shape[0])
     if not 1 <= k <= _native.WGATE_MAX_K:
         return k, (dims if k else np.zeros(1, dtype=np.int32)), np.zeros(2, dtype=np.float64)
-    m = _matrix(matrix, k, what)
-    mat = np.zeros(2 * m.size, dtype=np.float64)
-    mat[0::2], mat[1::2] = m.real.reshape(-1), m.imag.reshape(-1)
-    return k, dims, mat
+    return k, dims, _interleaved(_matrix(matrix, k, what))
 
 
 def _wgate_query(d, k, dims, mat, arrays=False):
@@ -55,8 +46,7 @@ def wide_gate_info(shape, strides, matrix, dims, dtype=torch.complex64):
     targets and the lowest other memory bits), tb (their number: 12 for complex64, 11 for complex128, or log2 of a smaller
     state), n_tiles, segment (elements of a contiguous piece of a tile), lds_bytes, table_bytes, bytes_read = bytes_written =
     bytes of the state, diagonal."""
-    if dtype not in _DTYPES:
-        raise TypeError(f"wide_gate_info: complex64 or complex128 expected, got {dtype}")
+    _dtype_code(dtype, "wide_gate_info")
     k, dims, mat = _split_gate(matrix, dims, len(shape), "wide_gate_info")
     info, target, tile = _wgate_query(_desc(shape, strides, dtype), k, dims, mat, arrays=True)
     return {"k": info.k, "target_bits": tuple(int(b) for b in target[:k]), "tile_bits": [int(b) for b in tile[:info.tile_bits]],
@@ -67,37 +57,24 @@ def wide_gate_info(shape, strides, matrix, dims, dtype=torch.complex64):
 
 def _wgate_pack(d, k, dims, mat):
     """The gate's table (include/artn.h) as a uint8 numpy array."""
-    info = _wgate_query(d, k, dims, mat)[0]
-    table = np.zeros(info.table_bytes // 8, dtype=np.uint64)
-    _native.check(_native.lib().artn_wgate_pack(ctypes.byref(d), k, _ptr(dims), _ptr(mat), _ptr(table), info.table_bytes))
-    return table.view(np.uint8), info
+    return _packed(_wgate_query(d, k, dims, mat)[0],
+                   lambda *table: _native.lib().artn_wgate_pack(ctypes.byref(d), k, _ptr(dims), _ptr(mat), *table))
 
 
-class WideGate:
+class WideGate(_Prebuilt):
     """One gate (matrix, dims), k = len(dims) in 1..5, for tensors of one layout.  Validates, plans, packs the table and copies it
     to `device` once; g(amps) then updates amps IN PLACE with one launch and returns it."""
 
     def __init__(self, shape, strides, dtype, matrix, dims, device):
-        if dtype not in _DTYPES:
-            raise TypeError(f"WideGate: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"WideGate: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, device)
         self.k, self._dims, mat = _split_gate(matrix, dims, len(self.shape), "WideGate")
         self._d = _desc(self.shape, self.strides, dtype)
         table, info = _wgate_pack(self._d, self.k, self._dims, mat)
         self.table_bytes, self.tile_bits, self.n_tiles = info.table_bytes, info.tile_bits, info.n_tiles
-        self._table = torch.from_numpy(table).to(self.device)
+        self._upload(table)
 
     def __call__(self, amps):
-        what = "wide_gates.WideGate"
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self._table.device:
-            raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {amps.device}")
+        self._check(amps, "wide_gates.WideGate")
         with torch.cuda.device(amps.device):
             _native.check(_native.lib().artn_wgate_apply(ctypes.byref(self._d), amps.data_ptr(), self.k, _ptr(self._dims),
                                                          self._table.data_ptr(), self.table_bytes,
@@ -118,7 +95,7 @@ def _width(gate, g):
     return 1 if isinstance(gate[1], (int, np.integer)) else len(gate[1])
 
 
-class FusedCircuit:
+class FusedCircuit(_Prebuilt):
     """An ordered list of gates [(matrix, dims), ...] of ANY width 1..5 for tensors of one layout.  The list is cut, in order,
     into maximal stretches of gates on one or two dims -- each ONE GateCircuit with the given max_rank -- and single gates on
     three to five dims -- each one WideGate; gates are never reordered, and wide gates are not fused into LDS runs.  A circuit
@@ -126,12 +103,7 @@ class FusedCircuit:
     the sum of the stretches' runs plus the number of wide gates."""
 
     def __init__(self, shape, strides, dtype, gates, device, max_rank=None):
-        if dtype not in _DTYPES:
-            raise TypeError(f"FusedCircuit: complex64 or complex128 expected, got {dtype}")
-        self.shape, self.strides, self.dtype = tuple(int(e) for e in shape), tuple(int(s) for s in strides), dtype
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"FusedCircuit: artensor_amd executes on MI355X only (got device {self.device}); there is no CPU fallback")
+        self._bind(shape, strides, dtype, device)
         gates = list(gates)
         if not gates:
             raise ValueError("at least one gate is needed")
@@ -152,13 +124,7 @@ class FusedCircuit:
         self.table_bytes = sum(p.table_bytes for p in self.parts)
 
     def __call__(self, amps):
-        what = "wide_gates.FusedCircuit"
-        _checked(amps, what)
-        if tuple(amps.shape) != self.shape or tuple(amps.stride()) != self.strides or amps.dtype != self.dtype:
-            raise ValueError(f"{what}: built for shape {self.shape}, strides {self.strides}, {self.dtype}; got "
-                             f"{tuple(amps.shape)}, {tuple(amps.stride())}, {amps.dtype}")
-        if amps.device != self.parts[0]._table.device:
-            raise ValueError(f"{what}: built for {self.parts[0]._table.device}, got a tensor on {amps.device}")
+        self.parts[0]._check(amps, "wide_gates.FusedCircuit")    # (no table of its own: a part has its layout, and a table)
         for part in self.parts:
             part(amps)
         return amps
