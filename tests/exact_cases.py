@@ -22,7 +22,8 @@ BITS, GENERIC = {"ARTN_FORCE_BITS": "1"}, {"ARTN_FORCE_GENERIC": "1"}
 
 class Case(dict):
     """name, kind ('step' | 'pair' | 'gather' | 'row_pairs' | 'acc_step' | 'acc_pair' | 'view'), cls, dtype ('complex64' | 'complex128'), precision (None |
-    'bf16'), eqs, a_shape, b_shapes, env, seed, plus what a kind needs (rows, view)"""
+    'bf16'), eqs, a_shape, b_shapes, env, seed, plus what a kind needs (rows, view); views: {'a' | 'b' | 'out' -> view kind}
+    of a case whose operands are views (view_cases; kind 'view': the three older cases, `view` on a and b)"""
     __getattr__ = dict.__getitem__
 
     @property
@@ -273,9 +274,96 @@ def cases():
         eq, sa, sb = bit_step(100 * k + n, k, n, ra)
         out.append(_case(f"generic_k{k}_n{n}", "step", both[k % 2], [eq], sa, [sb], env=GENERIC, seed=100 * k + n))
     out.append(_case("generic_extent4", "step", "dense", ["abcdefg,gcx->abdefx"], (4,) * 7, [(4, 4, 4)], env=GENERIC, seed=5))
+    out += view_cases()
     names = [c.name for c in out]
     assert len(set(names)) == len(names), sorted(n for n in names if names.count(n) > 1)
     return {c.name: c for c in out}
+
+
+VIEWS = {
+    "permuted": dict(a="permuted", b="permuted"), "inner": dict(a="inner", b="inner"), "ends": dict(a="ends", b="ends"),
+    "gap": dict(a="gap"), "offset16": dict(a="offset16", b="offset16", out="offset16"),
+    "offset8a": dict(a="offset8"), "offset8b": dict(b="offset8"), "offset8c": dict(out="offset8"),
+}
+
+
+def view_cases():
+    """The contraction kernels on operand views, storage offsets and 8-byte bases (view kinds: above view_of), at the smallest
+    shapes of the tables above; every launch writes into a result buffer inside sentinel margins"""
+    out = []
+    both = ("wide", "dense")
+
+    def add(name, kind, cls, eqs, sa, sbs, view, views=None, **more):
+        out.append(_case(f"v_{name}_{view}_{cls}", kind, cls, eqs, sa, sbs, views=views or VIEWS[view], **more))
+    # artn_k_bits, single steps with k = 1, 4, 6: every view kind
+    for k, n, ra in [(1, 1, 12), (4, 4, 15), (6, 6, 16)]:
+        eq, sa, sb = bit_step(100 * k + n, k, n, ra)
+        for view in VIEWS:
+            for cls in both:
+                add(f"bits_k{k}", "step", cls, [eq], sa, [sb], view, env=BITS, seed=100 * k + n)
+    # artn_k_bits128 (a single step) and the f64 GEMM
+    eq, sa, sb = bit_step(606, 6, 6, 16)
+    for view in ("permuted", "gap", "offset16"):
+        for cls in ("wide128", "dense"):
+            add("bits128_k6", "step", cls, [eq], sa, [sb], view, dtype="complex128", seed=606)
+    eq, sa, sb = bit_step(404, 4, 4, 15)
+    for view in ("permuted", "offset16"):
+        for cls in ("wide128", "dense"):
+            add("gemm128_k4", "step", cls, [eq], sa, [sb], view, dtype="complex128", env=BITS, seed=404)
+    # the two-operand GEMM: an 8-byte B is replanned inside artn_contract (the kernel moves both operands in 16-byte lanes)
+    m, n, k, batch = GEMM_STEPS[-1]
+    eq, sa, sb = gemm_step(1000 * m + 10 * n + k, m, n, k, batch)
+    for view in ("gap", "offset16", "offset8b"):
+        for cls in both:
+            add(f"gemm_m{m}_n{n}_k{k}_b{batch}", "step", cls, [eq], sa, [sb], view, seed=1000 * m + 10 * n + k)
+    eq, sa, sb = bit_step(706, 7, 6, 16)
+    for cls in both:
+        add("gemm_bits_k7", "step", cls, [eq], sa, [sb], "offset8b", env=BITS, seed=706)
+    # the extent GEMM and its row-streaming form
+    eq, sa, sb = extent_step(11, dict(m0=9, m1=5, m2=6, m3=2, m4=3, m5=5, m6=2), dict(n0=3, n1=6, n2=2), dict(k0=3, k1=5, k2=2))
+    for n_view, view in enumerate(("permuted", "offset16", "offset8b")):
+        add("xgemm_mixed", "step", both[n_view % 2], [eq], sa, [sb], view, seed=11)
+    for kk, nn, form, m_tile_bits in [(5, 16, 0, 6), (7, 41, 1, 4)]:
+        m1, m0 = 150, 221
+        if form == 0:
+            eq, sa, sb = (("k", "m1", "m0"), ("n", "k"), ("n", "m1", "m0")), (kk, m1, m0), (nn, kk)
+        else:
+            eq, sa, sb = (("m1", "m0", "k"), ("k", "n"), ("n", "m1", "m0")), (m1, m0, kk), (kk, nn)
+        for view in ("offset16", "offset8b"):
+            add(f"xrow_k{kk}_n{nn}", "step", both[form], [eq], sa, [sb], view, seed=2026 + kk, m_tile_bits=m_tile_bits)
+    # the packed-operand GEMM, bf16 and complex64
+    eq, sa, sb = gemm_step(100, 12, 11, 9)
+    for view in ("inner", "offset16"):
+        add("pgemm_bf16", "step", "bf16", [eq], sa, [sb], view, precision="bf16", seed=100)
+    eq, sa, sb = gemm_step(200, 12, 11, 11)
+    for view in ("inner", "offset16"):
+        add("pgemm_c64", "step", "dense", [eq], sa, [sb], view, seed=200)
+    # fused pairs 5 + 3 and 6 + 4: a non-contiguous A is declined by contract2 and runs as two launches, an offset one fuses
+    for k1, k2, ra in [(5, 3, 16), (6, 4, 17)]:
+        eqs, sa, sbs = bit_pair(1000 * k1 + 10 * k2, k1, k1, k2, k2, ra)
+        for view, cls in [("inner", "wide"), ("gap", "dense"), ("offset16", "wide"), ("offset16", "dense")]:
+            # (a pair's small operands stay as they are: only A decides whether contract2 fuses)
+            add(f"pair_{k1}_{k2}", "pair", cls, eqs, sa, sbs, view, views=dict(a=view), env=BITS, seed=10 * k1 + k2)
+    # gathered steps and row pairs: source rows out of an inner view; an 8-byte A goes through the callers' explicit gather
+    eq, sa, sb = gather_step(7, 5, 7, 12, 3, 2)
+    for view, cls in [("inner", "wide"), ("inner", "dense"), ("offset8a", "dense")]:
+        add("gather_7rows_k3", "gather", cls, [eq], sa, [sb], view, seed=30, rows=7)
+    for view, cls in [("inner", "wide"), ("inner", "dense"), ("offset8a", "wide")]:
+        add("row_pairs", "row_pairs", cls, ["zABCDEFGHIJKL,zLKJIab->zABCDEFGHab"], (16,) + (2,) * 12, [(16,) + (2,) * 6], view,
+            seed=41, rows=600)
+    # store-phase accumulation into a contiguous buffer at a storage offset: complex128 through the entry points themselves,
+    # complex64 through tensor_contraction(accumulate_into=), whose fallback adds with artn_axpy_c64 (an 8-byte accumulator
+    # always ends there: artn_contract_acc refuses it)
+    eq, sa, sb = bit_step(606, 6, 6, 16)
+    for cls in ("wide128", "dense"):
+        add("acc_step_c128", "acc_step", cls, [eq], sa, [sb], "offset16", dtype="complex128", seed=607)
+    eqs, sa, sbs = n30_pair(80, 83, 16)
+    for cls in ("wide128", "dense"):
+        add("acc_pair_80_83_c128", "acc_pair", cls, eqs, sa, sbs, "offset16", dtype="complex128", seed=480)
+    for view in ("offset16", "offset8c"):
+        for cls in both:
+            add("acc_step_k6", "acc_step", cls, [eq], sa, [sb], view, env=BITS, seed=608, wrapper=True)
+    return out
 
 
 def wide_pairs():
@@ -327,20 +415,115 @@ class environment:
         return False
 
 
+# ---- operand views -------------------------------------------------------------------------------------------------------------
+# A view is a recipe on a flat base of `offset + prod(base_shape)` elements: flat[offset:].reshape(base_shape), its dims
+# permuted by `perm`, then indexed with `index` -- the same three steps in numpy (the reference) and in torch (the device
+# operand), so the two share slicing syntax and nothing else.  View kinds, per operand ('a', 'b': the first small operand,
+# 'out': the result buffer or accumulator):
+#   permuted  a: base.permute(p) of a contiguous base, p drawn from the case's seed: dense, dims in another memory order; b: transposed
+#   inner     one index of an axis of extent 2 put in after five (a) / four (b) of the operand's own axes (fewer: before the last)
+#   ends      big_a[1, ..., 0] and big_b[..., 1]
+#   gap       a: base[..., ::2, ...] on its first free and its first contracted axis (never the last axis): every stride a power of
+#             two, one address bit skipped at each of the two; b as it is
+#   offset16  a contiguous operand 16 j bytes into its storage, j = 3 (a), 5 (b), 7 (out)
+#   offset8   complex64 only: a contiguous operand 8 bytes into its storage
+VIEW_KINDS = ("permuted", "inner", "ends", "gap", "offset16", "offset8")
+OFFSET16_J = {"a": 3, "b": 5, "out": 7}
+
+
+class Recipe(dict):
+    """base_shape, perm, index, offset (elements)"""
+    __getattr__ = dict.__getitem__
+
+    @property
+    def numel(self):
+        """elements of the flat base, offset included"""
+        return self.offset + int(np.prod(self.base_shape, dtype=np.int64))
+
+
+def _recipe(base_shape, perm=None, index=(), offset=0):
+    base_shape = tuple(int(x) for x in base_shape)
+    return Recipe(base_shape=base_shape, perm=tuple(perm) if perm is not None else tuple(range(len(base_shape))), index=tuple(index), offset=offset)
+
+
+def apply_view(r, flat, shift=0):
+    """the view of recipe r in a flat numpy array or torch tensor; shift: elements in front of the base (a guard margin)"""
+    n = int(np.prod(r.base_shape, dtype=np.int64))
+    x = flat[shift + r.offset:shift + r.offset + n].reshape(r.base_shape)
+    x = x.permute(*r.perm) if hasattr(x, "permute") else x.transpose(r.perm)
+    return x[r.index] if r.index else x
+
+
+def _view_recipe(case, which, shape):
+    views = {"a": case.view, "b": case.view} if case.kind == "view" else case.get("views", {})
+    kind = views.get(which)
+    nd = len(shape)
+    itemsize = 16 if case.dtype == "complex128" else 8
+    if kind is None:
+        return _recipe(shape)
+    assert kind in VIEW_KINDS, kind
+    if kind == "inner" and which != "out":
+        pos = min(5 if which == "a" else 4, nd - 1)
+        return _recipe(shape[:pos] + (2,) + shape[pos:], index=(slice(None),) * pos + (1 if which == "a" else 0,))
+    if kind == "ends" and which != "out":
+        return _recipe((2,) + shape + (2,), index=(1, Ellipsis, 0)) if which == "a" else _recipe(shape + (2,), index=(Ellipsis, 1))
+    if kind == "permuted" and which != "out":
+        p = np.random.default_rng(case.seed + 7).permutation(nd) if which == "a" else np.arange(nd)[::-1]
+        base = [0] * nd
+        for i in range(nd):
+            base[p[i]] = shape[i]     # base.permute(p).shape[i] == base.shape[p[i]]
+        return _recipe(base, perm=[int(x) for x in p])
+    if kind == "gap" and which == "a":
+        la, lb, lo = X.labels(case.eqs[0])
+        free = [n for n, x in enumerate(la[:-1]) if x not in lb]
+        con = [n for n, x in enumerate(la[:-1]) if x in lb and x not in lo]
+        axes = (free[0], con[0])
+        return _recipe([2 * e if n in axes else e for n, e in enumerate(shape)],
+                       index=tuple(slice(None, None, 2) if n in axes else slice(None) for n in range(max(axes) + 1)))
+    if kind == "offset16":
+        return _recipe(shape, offset=OFFSET16_J[which] * 16 // itemsize)
+    if kind == "offset8":
+        assert case.dtype == "complex64", "an 8-byte base exists for complex64 only"
+        return _recipe(shape, offset=1)
+    return _recipe(shape)     # (a kind that shapes one operand only leaves the others as they are)
+
+
+def has_views(case):
+    return case.kind == "view" or bool(case.get("views"))
+
+
 def view_of(case):
-    """(shape of the base of a, index of the view in it, the same for b) of a 'view' case: 'inner' fixes one index of an axis
-    put in after five (a) / four (b) of the operand's own, 'ends' is big_a[1, ..., 0] and big_b[..., 1]"""
-    sa, sb = case.a_shape, case.b_shapes[0]
-    if case.view == "inner":
-        return (sa[:5] + (2,) + sa[5:], (slice(None),) * 5 + (1,)), (sb[:4] + (2,) + sb[4:], (slice(None),) * 4 + (0,))
-    return ((2,) + sa + (2,), (1, Ellipsis, 0)), (sb + (2,), (Ellipsis, 1))
+    """{'a', 'b', 'out'} -> Recipe of the case's streamed operand, first small operand and result buffer (plain cases: the
+    contiguous operand at offset 0)"""
+    out_shape = result_shape(case)
+    if case.kind in ("gather", "row_pairs"):   # (one result row per index pair)
+        out_shape = (case.rows,) + out_shape[1:]
+    return {"a": _view_recipe(case, "a", case.a_shape), "b": _view_recipe(case, "b", case.b_shapes[0]),
+            "out": _view_recipe(case, "out", out_shape)}
+
+
+def view_layout(r, itemsize):
+    """(element strides, byte offset of the first element mod 16, contiguous) of a recipe's view, from numpy's own slicing of
+    an array of that element size"""
+    flat = np.empty(r.numel, dtype=np.complex128 if itemsize == 16 else np.complex64)
+    v = apply_view(r, flat)
+    first = v.__array_interface__["data"][0] - flat.__array_interface__["data"][0]
+    return tuple(s // itemsize for s in v.strides), first % 16, bool(v.flags["C_CONTIGUOUS"])
 
 
 def view_strides(case):
-    """element strides of the two views"""
-    (bsa, ia), (bsb, ib) = view_of(case)
-    st = lambda shape, idx: tuple(s // 16 for s in np.empty(shape, dtype=np.complex128)[idx].strides)
-    return st(bsa, ia), st(bsb, ib)
+    """element strides of the views of a and b"""
+    v = view_of(case)
+    itemsize = 16 if case.dtype == "complex128" else 8
+    return view_layout(v["a"], itemsize)[0], view_layout(v["b"], itemsize)[0]
+
+
+def embed(r, value, rng, kind):
+    """A flat base for recipe r that holds `value` in the view's elements and drawn non-zero integers (below 2^7: they fit every
+    dtype and precision) everywhere else: a kernel that reads one stride off the view reads one of them"""
+    flat = X.draw_a(rng, (r.numel,), "bf16", kind, bits=127)
+    apply_view(r, flat)[...] = value
+    return flat
 
 
 def planned(case):
@@ -353,8 +536,21 @@ def planned(case):
     from artensor_amd import contraction as C
     dtype = torch.complex128 if case.dtype == "complex128" else torch.complex64
     env = dict(case.env, ARTN_FORCE_BITS="1") if case.kind == "gather" else case.env
+    views = case.get("views", {})
+    if "offset8" in (views.get("a"), views.get("out")) and case.kind == "step":
+        # artn_contract plans an 8-byte aligned A or C with the tiled kernels switched off, as ARTN_FORCE_GENERIC does; the query
+        # sees no pointers, so the switch stands in for them here (an 8-byte B changes the plan of the two-operand GEMM only,
+        # inside the call: PLANNED holds the query's answer for those cases)
+        env = dict(env, ARTN_FORCE_GENERIC="1")
+    strided = has_views(case) and case.kind in ("step", "view", "pair")
+    sa, sb = view_strides(case) if strided else (None, None)
     with environment(env), A.precision(case.precision):
-        if case.kind in ("pair", "acc_pair"):
+        if case.kind == "pair" and not view_layout(view_of(case)["a"], 8)[2]:
+            # contract2 declines a non-contiguous A: the first of the two launches that run instead
+            info = A.step_info(case.eqs[0], case.a_shape, case.b_shapes[0], dtype=dtype, a_stride=sa, b_stride=sb)
+        elif case.kind == "step" and strided:
+            info = A.step_info(case.eqs[0], case.a_shape, case.b_shapes[0], dtype=dtype, a_stride=sa, b_stride=sb)
+        elif case.kind in ("pair", "acc_pair"):
             info = C.pair_info(case.eqs[0], case.a_shape, case.b_shapes[0], case.eqs[1], case.b_shapes[1], dtype=dtype)
         elif case.kind == "row_pairs":   # (the unbatched step on the distinct rows: two private labels in place of the batch label)
             la, lb, lo = X.labels(case.eqs[0])
@@ -363,7 +559,6 @@ def planned(case):
         elif case.kind == "gather":
             info = A.step_info(case.eqs[0], (case.rows,) + case.a_shape[1:], (case.rows,) + case.b_shapes[0][1:], dtype=dtype)
         elif case.kind == "view":
-            sa, sb = view_strides(case)
             info = A.step_info(case.eqs[0], case.a_shape, case.b_shapes[0], dtype=dtype, a_stride=sa, b_stride=sb)
         else:
             info = A.step_info(case.eqs[0], case.a_shape, case.b_shapes[0], dtype=dtype)
@@ -373,9 +568,9 @@ def planned(case):
 
 
 def operands(case):
-    """(a, [small operands], accumulator or None, rows or None) of a case, from its seed.  'view' cases: a and the small operand
-    are the views big_a[1, ..., 0] and big_b[..., 1] of bigger arrays (numpy views: the GPU test slices device copies of the
-    bases the same way); 'gather' cases: a and b hold the source rows, rows = (rows_a, rows_b)."""
+    """(a, [small operands], accumulator or None, rows or None) of a case, from its seed.  Cases with views (has_views): a and
+    the first small operand are the flat bases of their recipes (view_of; apply_view gives the operand, and the GPU test slices
+    device copies of the bases the same way); 'gather' cases: a and b hold the source rows, rows = (rows_a, rows_b)."""
     stages = list(zip(case.eqs, case.b_shapes))
     kind = case.arith_kind
     acc = case.kind in ("acc_pair", "acc_step")
@@ -383,12 +578,19 @@ def operands(case):
         la, lb, lo = X.labels(case.eqs[0])
         rng = np.random.default_rng(case.seed)
         k = int(np.prod([dict(zip(lb, case.b_shapes[0]))[x] for x in X.contracted_labels(case.eqs[0])]))
-        (bsa, ia), (bsb, ib) = view_of(case)
+        v = view_of(case)
+        bsa, bsb, ib = v["a"].base_shape, v["b"].base_shape, v["b"].index
         a = X.draw_a(rng, bsa, case.cls, kind, bits=X.a_bits(case.cls, kind, [k]))
         # (the base of b by the class rule on the view's own labels plus the extra axis: every view of it keeps the rule)
         extra = len(ib) - 1 if ib[0] is not Ellipsis else len(lb)
         b = X.draw_small(rng, lb[:extra] + ("v",) + lb[extra:], bsb, X.contracted_labels(case.eqs[0]), case.cls, kind)
-        return a, [b], None, None
+        return a.reshape(-1), [b.reshape(-1)], None, None
+    if has_views(case):
+        # the operands of the same case without views, each put into a base of drawn values: the views keep their class rules
+        plain = Case(case, views={})
+        a, smalls, acc, rows = operands(plain)
+        v, rng = view_of(case), np.random.default_rng(case.seed + 3)
+        return embed(v["a"], a, rng, kind), [embed(v["b"], smalls[0], rng, kind)] + smalls[1:], acc, rows
     if case.kind in ("gather", "row_pairs"):
         # (the rows of the operands: every source row is a stage operand of its own, so the class rules hold per row)
         a, smalls = X.draw_chain(case.seed, case.cls, kind, stages, case.a_shape)
@@ -413,9 +615,9 @@ def exact_result(case, ops=None):
     """(exact result as complex128, accumulator start or None, largest range quantity) of a case, in integers"""
     a, smalls, acc, rows = ops if ops is not None else operands(case)
     kind = case.arith_kind
-    if case.kind == "view":
-        (_, ia), (_, ib) = view_of(case)
-        a, smalls = a[ia], [smalls[0][ib]]
+    if has_views(case):
+        v = view_of(case)
+        a, smalls = apply_view(v["a"], a), [apply_view(v["b"], smalls[0])] + list(smalls[1:])
     if case.kind in ("gather", "row_pairs"):
         la, lb, lo = X.labels(case.eqs[0])
         row_eq = (la[1:], lb[1:], lo[1:])
@@ -664,4 +866,104 @@ PLANNED = {
     "generic_k3_n3": (0, -1, 0, 0, 0),
     "generic_k7_n3": (0, -1, 0, 0, 0),
     "generic_extent4": (0, -1, 0, 0, 0),
+    # operand views, storage offsets and 8-byte bases (view_cases)
+    "v_bits_k1_permuted_wide": (1, 0, 1, 0, 0),
+    "v_bits_k1_permuted_dense": (1, 0, 1, 0, 0),
+    "v_bits_k1_inner_wide": (1, 0, 1, 0, 0),
+    "v_bits_k1_inner_dense": (1, 0, 1, 0, 0),
+    "v_bits_k1_ends_wide": (5, 1, 4, 0, 0),
+    "v_bits_k1_ends_dense": (5, 1, 4, 0, 0),
+    "v_bits_k1_gap_wide": (1, 0, 1, 0, 0),
+    "v_bits_k1_gap_dense": (1, 0, 1, 0, 0),
+    "v_bits_k1_offset16_wide": (1, 0, 1, 0, 0),
+    "v_bits_k1_offset16_dense": (1, 0, 1, 0, 0),
+    "v_bits_k1_offset8a_wide": (0, -1, 0, 0, 0),
+    "v_bits_k1_offset8a_dense": (0, -1, 0, 0, 0),
+    "v_bits_k1_offset8b_wide": (1, 0, 1, 0, 0),
+    "v_bits_k1_offset8b_dense": (1, 0, 1, 0, 0),
+    "v_bits_k1_offset8c_wide": (0, -1, 0, 0, 0),
+    "v_bits_k1_offset8c_dense": (0, -1, 0, 0, 0),
+    "v_bits_k4_permuted_wide": (1, 0, 4, 0, 0),
+    "v_bits_k4_permuted_dense": (1, 0, 4, 0, 0),
+    "v_bits_k4_inner_wide": (1, 0, 4, 0, 0),
+    "v_bits_k4_inner_dense": (1, 0, 4, 0, 0),
+    "v_bits_k4_ends_wide": (5, 1, 4, 0, 0),
+    "v_bits_k4_ends_dense": (5, 1, 4, 0, 0),
+    "v_bits_k4_gap_wide": (1, 0, 4, 0, 0),
+    "v_bits_k4_gap_dense": (1, 0, 4, 0, 0),
+    "v_bits_k4_offset16_wide": (1, 0, 4, 0, 0),
+    "v_bits_k4_offset16_dense": (1, 0, 4, 0, 0),
+    "v_bits_k4_offset8a_wide": (0, -1, 0, 0, 0),
+    "v_bits_k4_offset8a_dense": (0, -1, 0, 0, 0),
+    "v_bits_k4_offset8b_wide": (1, 0, 4, 0, 0),
+    "v_bits_k4_offset8b_dense": (1, 0, 4, 0, 0),
+    "v_bits_k4_offset8c_wide": (0, -1, 0, 0, 0),
+    "v_bits_k4_offset8c_dense": (0, -1, 0, 0, 0),
+    "v_bits_k6_permuted_wide": (1, 1, 6, 0, 0),
+    "v_bits_k6_permuted_dense": (1, 1, 6, 0, 0),
+    "v_bits_k6_inner_wide": (1, 1, 6, 0, 0),
+    "v_bits_k6_inner_dense": (1, 1, 6, 0, 0),
+    "v_bits_k6_ends_wide": (5, 1, 4, 0, 0),
+    "v_bits_k6_ends_dense": (5, 1, 4, 0, 0),
+    "v_bits_k6_gap_wide": (1, 1, 6, 0, 0),
+    "v_bits_k6_gap_dense": (1, 1, 6, 0, 0),
+    "v_bits_k6_offset16_wide": (1, 1, 6, 0, 0),
+    "v_bits_k6_offset16_dense": (1, 1, 6, 0, 0),
+    "v_bits_k6_offset8a_wide": (0, -1, 0, 0, 0),
+    "v_bits_k6_offset8a_dense": (0, -1, 0, 0, 0),
+    "v_bits_k6_offset8b_wide": (1, 1, 6, 0, 0),
+    "v_bits_k6_offset8b_dense": (1, 1, 6, 0, 0),
+    "v_bits_k6_offset8c_wide": (0, -1, 0, 0, 0),
+    "v_bits_k6_offset8c_dense": (0, -1, 0, 0, 0),
+    "v_bits128_k6_permuted_wide128": (1, 3, 6, 0, 0),
+    "v_bits128_k6_permuted_dense": (1, 3, 6, 0, 0),
+    "v_bits128_k6_gap_wide128": (1, 3, 6, 0, 0),
+    "v_bits128_k6_gap_dense": (1, 3, 6, 0, 0),
+    "v_bits128_k6_offset16_wide128": (1, 3, 6, 0, 0),
+    "v_bits128_k6_offset16_dense": (1, 3, 6, 0, 0),
+    "v_gemm128_k4_permuted_wide128": (2, 3, 4, 0, 0),
+    "v_gemm128_k4_permuted_dense": (2, 3, 4, 0, 0),
+    "v_gemm128_k4_offset16_wide128": (2, 3, 4, 0, 0),
+    "v_gemm128_k4_offset16_dense": (2, 3, 4, 0, 0),
+    "v_gemm_m8_n8_k7_b3_gap_wide": (2, 0, 7, 0, 0),
+    "v_gemm_m8_n8_k7_b3_gap_dense": (2, 0, 7, 0, 0),
+    "v_gemm_m8_n8_k7_b3_offset16_wide": (2, 0, 7, 0, 0),
+    "v_gemm_m8_n8_k7_b3_offset16_dense": (2, 0, 7, 0, 0),
+    "v_gemm_m8_n8_k7_b3_offset8b_wide": (2, 0, 7, 0, 0),
+    "v_gemm_m8_n8_k7_b3_offset8b_dense": (2, 0, 7, 0, 0),
+    "v_gemm_bits_k7_offset8b_wide": (2, 0, 7, 0, 0),
+    "v_gemm_bits_k7_offset8b_dense": (2, 0, 7, 0, 0),
+    "v_xgemm_mixed_permuted_wide": (5, 1, 4, 0, 0),
+    "v_xgemm_mixed_offset16_dense": (5, 1, 4, 0, 0),
+    "v_xgemm_mixed_offset8b_wide": (5, 1, 4, 0, 0),
+    "v_xrow_k5_n16_offset16_wide": (5, 1, 4, 0, 0),
+    "v_xrow_k5_n16_offset8b_wide": (5, 1, 4, 0, 0),
+    "v_xrow_k7_n41_offset16_dense": (5, 1, 4, 0, 0),
+    "v_xrow_k7_n41_offset8b_dense": (5, 1, 4, 0, 0),
+    "v_pgemm_bf16_inner_bf16": (4, 2, 9, 0, 0),
+    "v_pgemm_bf16_offset16_bf16": (4, 2, 9, 0, 0),
+    "v_pgemm_c64_inner_dense": (4, 1, 11, 0, 0),
+    "v_pgemm_c64_offset16_dense": (4, 1, 11, 0, 0),
+    "v_pair_5_3_inner_wide": (1, 1, 5, 0, 0),
+    "v_pair_5_3_gap_dense": (1, 1, 5, 0, 0),
+    "v_pair_5_3_offset16_wide": (1, 1, 5, 3, 0),
+    "v_pair_5_3_offset16_dense": (1, 1, 5, 3, 0),
+    "v_pair_6_4_inner_wide": (1, 1, 6, 0, 0),
+    "v_pair_6_4_gap_dense": (1, 1, 6, 0, 0),
+    "v_pair_6_4_offset16_wide": (1, 1, 6, 4, 0),
+    "v_pair_6_4_offset16_dense": (1, 1, 6, 4, 0),
+    "v_gather_7rows_k3_inner_wide": (1, 0, 3, 0, 0),
+    "v_gather_7rows_k3_inner_dense": (1, 0, 3, 0, 0),
+    "v_gather_7rows_k3_offset8a_dense": (1, 0, 3, 0, 0),
+    "v_row_pairs_inner_wide": (1, 0, 4, 0, 0),
+    "v_row_pairs_inner_dense": (1, 0, 4, 0, 0),
+    "v_row_pairs_offset8a_wide": (1, 0, 4, 0, 0),
+    "v_acc_step_c128_offset16_wide128": (1, 3, 6, 0, 0),
+    "v_acc_step_c128_offset16_dense": (1, 3, 6, 0, 0),
+    "v_acc_pair_80_83_c128_offset16_wide128": (1, 3, 3, 4, 0),
+    "v_acc_pair_80_83_c128_offset16_dense": (1, 3, 3, 4, 0),
+    "v_acc_step_k6_offset16_wide": (1, 1, 6, 0, 0),
+    "v_acc_step_k6_offset16_dense": (1, 1, 6, 0, 0),
+    "v_acc_step_k6_offset8c_wide": (1, 1, 6, 0, 0),
+    "v_acc_step_k6_offset8c_dense": (1, 1, 6, 0, 0),
 }

@@ -26,7 +26,8 @@ def _einsum128(eq, a, b):
     for x in la + lb + lo:
         sym.setdefault(x, chr(65 + len(sym)) if len(sym) < 26 else chr(97 + len(sym) - 26))
     s = "".join(sym[x] for x in la) + "," + "".join(sym[x] for x in lb) + "->" + "".join(sym[x] for x in lo)
-    return np.einsum(s, np.asarray(a, dtype=np.complex128), np.asarray(b, dtype=np.complex128))
+    big = np.size(a) * np.size(b) > 2 ** 36   # (the packed GEMM's shapes: through BLAS, the same integers below 2^53)
+    return np.einsum(s, np.asarray(a, dtype=np.complex128), np.asarray(b, dtype=np.complex128), optimize=big)
 
 
 @pytest.mark.parametrize("seed", range(44))
@@ -161,6 +162,92 @@ def test_planned_paths():
     for k in (E.KERNEL_GEMM, E.KERNEL_BITS, E.KERNEL_GENERIC):
         assert {cases[n].cls for n in c128 if P[n]["kernel"] == k} == {"wide128", "dense"}
     assert len(sel(lambda c, p: c64(c) and p["kernel"] == E.KERNEL_GENERIC and "ARTN_FORCE_GENERIC" in c.env)) == 3
+
+
+VIEW_CASES = [n for n, c in E.cases().items() if E.has_views(c)]
+
+
+def test_view_cases_reach_every_kernel_family():
+    """At least two cases with an operand view, a storage offset or an 8-byte B are planned on each of artn_k_bits,
+    artn_k_bits128, the two-operand GEMM, the f64 GEMM, the extent GEMM and the packed GEMM themselves (cases the planner sends
+    to the strided kernel -- an 8-byte A or C, by design -- do not count), every view kind is in use, and the three older view
+    cases are still there."""
+    cases = E.cases()
+    assert {"gemm_views_wide", "gemm_views_dense", "xgemm_views_dense"} <= set(VIEW_CASES)
+    count = {}
+    for n in VIEW_CASES:
+        c, (kernel, arith) = cases[n], E.PLANNED[n][:2]
+        if c.kind not in ("step", "view"):
+            continue
+        family = {(E.KERNEL_BITS, False): "bits", (E.KERNEL_BITS, True): "bits128", (E.KERNEL_GEMM, False): "gemm", (E.KERNEL_GEMM, True): "gemm128",
+                  (E.KERNEL_XGEMM, False): "xgemm", (E.KERNEL_XGEMM, True): "xgemm", (E.KERNEL_PGEMM, False): "pgemm"}.get((kernel, arith == 3))
+        if family:
+            count[family] = count.get(family, 0) + 1
+    assert set(count) == {"bits", "bits128", "gemm", "gemm128", "xgemm", "pgemm"} and min(count.values()) >= 2, count
+    used = {kind for n in VIEW_CASES for kind in cases[n].get("views", {}).values()}
+    assert used == set(E.VIEW_KINDS), used
+    for which in ("a", "b", "out"):   # an 8-byte base under A alone, B alone and the result alone
+        assert any(cases[n].get("views") == {which: "offset8"} for n in VIEW_CASES), which
+    assert {cases[n].m_tile_bits for n in VIEW_CASES if "m_tile_bits" in cases[n]} == {4, 6}   # the row-streaming forms
+    assert {cases[n].precision for n in VIEW_CASES if E.PLANNED[n][0] == E.KERNEL_PGEMM} == {"bf16", None}
+    kinds = {cases[n].kind for n in VIEW_CASES}
+    assert kinds == {"view", "step", "pair", "gather", "row_pairs", "acc_step", "acc_pair"}, kinds
+    # a gap skips an address bit and keeps every stride a power of two; a permuted A is dense
+    for n in VIEW_CASES:
+        c = cases[n]
+        r = E.view_of(c)["a"]
+        strides, _, contiguous = E.view_layout(r, 8)
+        if c.get("views", {}).get("a") == "gap":
+            assert all(s & (s - 1) == 0 for s in strides) and not contiguous and r.numel == 4 * int(np.prod(c.a_shape)), n
+        if c.get("views", {}).get("a") == "permuted":
+            assert sorted(strides) == sorted(E.view_layout(E._recipe(r.base_shape), 8)[0]) and not contiguous, n
+
+
+@pytest.mark.parametrize("name", VIEW_CASES)
+def test_view_slicing_is_torch_s_own(name):
+    """The strides, the 16-byte phase of the first element and the contiguity that view_layout reads off numpy are what torch
+    gives for the same recipe on a CPU tensor: the GPU test asserts them on what it passes to the library."""
+    import torch
+    case = E.cases()[name]
+    dt = torch.complex128 if case.dtype == "complex128" else torch.complex64
+    for which, r in E.view_of(case).items():
+        flat = torch.empty(r.numel, dtype=dt)
+        t = E.apply_view(r, flat)
+        strides, phase, contiguous = E.view_layout(r, flat.element_size())
+        assert tuple(t.stride()) == strides and t.is_contiguous() == contiguous, (which, tuple(t.stride()), strides)
+        assert (t.data_ptr() - flat.data_ptr()) % 16 == phase, which
+        rows = (case.rows,) if case.kind in ("gather", "row_pairs") else E.result_shape(case)[:1]
+        want_shape = {"a": case.a_shape, "b": case.b_shapes[0], "out": rows + E.result_shape(case)[1:]}[which]
+        assert tuple(t.shape) == tuple(want_shape), which
+    a_kind, out_kind = case.get("views", {}).get("a"), case.get("views", {}).get("out")
+    if a_kind in ("offset16", "offset8"):
+        assert E.view_layout(E.view_of(case)["a"], 8 if dt == torch.complex64 else 16)[1:] == (0 if a_kind == "offset16" else 8, True)
+    if out_kind == "offset8":
+        assert E.view_layout(E.view_of(case)["out"], 8)[1:] == (8, True)
+
+
+@pytest.mark.parametrize("name", VIEW_CASES)
+def test_view_references_against_numpy_einsum(name):
+    """exact_result of every case with views against complex128 np.einsum on the materialised (copied) views, and the base
+    around the views holds no zero: a read one stride off the view changes the result"""
+    case = E.cases()[name]
+    a, smalls, acc, rows = ops = E.operands(case)
+    want, start, _ = E.exact_result(case, ops)
+    v = E.view_of(case)
+    va, vb = np.ascontiguousarray(E.apply_view(v["a"], a)), np.ascontiguousarray(E.apply_view(v["b"], smalls[0]))
+    assert va.shape == case.a_shape and vb.shape == case.b_shapes[0]
+    if case.kind != "view":
+        outside = np.ones(a.shape, dtype=bool)
+        E.apply_view(v["a"], outside)[...] = False
+        assert np.all(a[outside] != 0)
+    if rows is not None:
+        va, vb = va[rows[0]], vb[rows[1]]
+    got = _einsum128(case.eqs[0], va, vb)
+    if len(case.eqs) == 2:
+        got = _einsum128(case.eqs[1], got, smalls[1])
+    if start is not None:
+        got = got + start.astype(np.complex128)
+    assert np.array_equal(got, want)
 
 
 def test_pairs_of_11_or_more_contracted_bits_fuse_on_the_wide_kernel_only():

@@ -10,7 +10,10 @@ lane of one small output, fails here although it passes the 1e-5 max-norm tolera
 
 Every case of tests/exact_cases.py first asserts its path from the planner's own answer (PLANNED), then the exactness
 condition on the reference alone, then np.array_equal.  A case that is planned onto another kernel fails; none is skipped
-(fused triples excepted, on builds without them: that test runs on development builds only).  Each test prints the largest range quantity as a power of two."""
+(fused triples excepted, on builds without them: that test runs on development builds only).  Each test prints the largest range quantity as a power of two.
+
+Cases with operand views, storage offsets and 8-byte bases (exact_cases.view_cases) run through run_view_case: operands sliced
+out of device copies of the reference's bases, layout asserted, everything inside guard margins that must come back unchanged."""
 import ctypes
 import functools
 import os
@@ -64,11 +67,6 @@ def run_case(case, a, smalls, start, rows):
                 la, lb, lo = X.labels(case.eqs[0])
                 assert C._big_k_outer(la, lb, lo, tuple(ta.shape), tuple(ta.stride()), tuple(tb.shape), tuple(tb.stride()), dt), "no split-K"
             got = A.contract(case.eqs[0], ta, tb)
-        elif case.kind == "view":
-            (_, ia), (_, ib) = E.view_of(case)
-            ta, tb = gpu(a)[ia], gpu(smalls[0])[ib]
-            assert not ta.is_contiguous() and (tuple(ta.stride()), tuple(tb.stride())) == E.view_strides(case)
-            got = A.contract(case.eqs[0], ta, tb)
         elif case.kind == "pair":
             got = C.contract2(case.eqs[0], gpu(a), gpu(smalls[0]), case.eqs[1], gpu(smalls[1]))
             assert got is not None, "the planner declined the pair"
@@ -104,13 +102,130 @@ def run_case(case, a, smalls, start, rows):
     return got.cpu().numpy()
 
 
+MARGIN = 64               # guard elements on either side of every base and result buffer (a multiple of 16 bytes)
+SENTINEL = complex(-77.0, 13.0)
+
+
+def _bits(t):
+    """the elements of a complex tensor as integer pairs: comparisons bit for bit"""
+    return torch.view_as_real(t).view(torch.int32 if t.dtype == torch.complex64 else torch.int64)
+
+
+class Guarded:
+    """The device operand of a view recipe (exact_cases.view_of): its flat base between two margins of SENTINEL, sliced as
+    numpy slices the reference's base, with the strides, the 16-byte phase of the pointer and the contiguity that numpy gives
+    asserted on what is passed -- a `.contiguous()` on the way would change all three.  flat None: a result buffer, SENTINEL
+    throughout.  assert_untouched compares the whole storage with its image from before the call, bit for bit; written=True
+    leaves out the view's own elements, the only ones a launch may change."""
+
+    def __init__(self, recipe, dtype, flat=None):
+        self.recipe = recipe
+        self.store = torch.full((2 * MARGIN + recipe.numel,), SENTINEL, dtype=dtype, device=DEV)
+        if flat is not None:
+            assert flat.shape == (recipe.numel,)
+            self.store[MARGIN:MARGIN + recipe.numel] = torch.from_numpy(flat).to(DEV)
+        self.view = E.apply_view(recipe, self.store, shift=MARGIN)
+        strides, phase, contiguous = E.view_layout(recipe, self.store.element_size())
+        assert tuple(self.view.stride()) == strides, (tuple(self.view.stride()), strides)
+        assert self.view.data_ptr() % 16 == phase and self.view.is_contiguous() == contiguous, (self.view.data_ptr() % 16, phase, contiguous)
+        self.snapshot()
+
+    def snapshot(self):
+        self.image = self.store.clone()
+
+    def fill(self, values):
+        self.view.copy_(gpu(values))
+        self.snapshot()
+
+    def assert_untouched(self, written=False):
+        same = (_bits(self.store) == _bits(self.image)).all(dim=1)
+        if written:
+            own = torch.zeros_like(same)
+            E.apply_view(self.recipe, own, shift=MARGIN)[...] = True
+            same |= own
+        assert bool(same.all()), (int((~same).sum()), "elements outside the view changed")
+
+
+class _Launches:
+    def __init__(self):
+        self.infos = []
+
+    def record(self, info, e0, e1):
+        self.infos.append(info)
+
+
+def run_view_case(case, a, smalls, start, rows):
+    """the launch of a case with operand views: every operand and the result inside guard margins"""
+    dt = torch.complex128 if case.dtype == "complex128" else torch.complex64
+    v = E.view_of(case)
+    ga, gb, go = Guarded(v["a"], dt, a), Guarded(v["b"], dt, smalls[0]), Guarded(v["out"], dt)
+    ta, tb, out = ga.view, gb.view, go.view
+    eq = case.eqs[0]
+    stream = N.current_stream_ptr(torch.device(DEV))
+    with E.environment(case.env), A.precision(case.precision):
+        if case.kind in ("step", "view"):
+            assert case.kind != "view" or not ta.is_contiguous()
+            assert A.contract(eq, ta, tb, out=out) is out
+        elif case.kind == "pair":
+            b2 = gpu(smalls[1])
+            C.profiler = seen = _Launches()
+            try:
+                got = C.contract2(eq, ta, tb, case.eqs[1], b2)
+                if ta.is_contiguous():   # (at a 16-byte offset: still one launch)
+                    assert got is not None and len(seen.infos) == 1 and seen.infos[0]["k2_bits"] == E.PLANNED[case.name][3] > 0, seen.infos
+                else:                    # declined: the caller runs the two steps one after the other
+                    assert got is None and seen.infos == []
+                    got = A.contract(case.eqs[1], A.contract(eq, ta, tb), b2)
+                    assert len(seen.infos) == 2 and all(i["k2_bits"] == 0 for i in seen.infos), seen.infos
+                    assert tuple(seen.infos[0][f] for f in E.INFO_FIELDS) == E.PLANNED[case.name]
+            finally:
+                C.profiler = None
+            out.copy_(got)
+        elif case.kind == "gather":
+            ra, rb = (torch.from_numpy(r) for r in rows)
+            if tb.data_ptr() % 16 == ta.data_ptr() % 16 == 0:
+                assert C.contract_gathered(eq, ta, ra, tb, rb, out=out) is out, "the gathered step does not fit the tiled kernels"
+            else:   # refused (nothing written); the sparse executor's chunk loop then gathers both operands explicitly
+                assert C.contract_gathered(eq, ta, ra, tb, rb, out=out) is None
+                go.assert_untouched()
+                tensors = {0: ta, 1: tb}
+                C._sparse_step(tensors, ((0, 1), eq, ([ra[:3], ra[3:]], [rb[:3], rb[3:]]), None))
+                out.copy_(tensors[0])
+        elif case.kind == "row_pairs":
+            ra, rb = (torch.from_numpy(r) for r in rows)
+            assert C.contract_row_pairs(eq, ta, ra, tb, rb, out=out) is out, "the pairs do not re-use rows enough"
+        elif case.kind == "acc_step" and case.get("wrapper"):
+            go.fill(start)
+            assert A.tensor_contraction({0: ta, 1: tb}, [((0, 1), eq)], accumulate_into=out) is out
+        elif case.kind == "acc_step":
+            go.fill(start)
+            la, lb, lo = X.labels(eq)
+            d, out_shape = C._descriptor(la, lb, lo, tuple(ta.shape), tuple(ta.stride()), tuple(tb.shape), tuple(tb.stride()), dt)
+            assert tuple(out_shape) == tuple(out.shape)
+            rc = N.lib().artn_contract_acc(ctypes.byref(d), ta.data_ptr(), tb.data_ptr(), out.data_ptr(), stream)
+            assert rc == 0, (rc, N.lib().artn_last_error())
+        elif case.kind == "acc_pair":
+            go.fill(start)
+            b2 = gpu(smalls[1])
+            d1, d2, out_shape = C._pair_descriptors(eq, ta, tb, case.eqs[1], b2)
+            assert tuple(out_shape) == tuple(out.shape)
+            rc = N.lib().artn_contract2_acc(ctypes.byref(d1), ctypes.byref(d2), ta.data_ptr(), tb.data_ptr(), b2.data_ptr(), out.data_ptr(), stream)
+            assert rc == 0, (rc, N.lib().artn_last_error())
+        else:
+            raise AssertionError(case.kind)
+    ga.assert_untouched()
+    gb.assert_untouched()
+    go.assert_untouched(written=True)
+    return out.cpu().numpy()
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_exact_case(name):
     case = CASES[name]
     assert_planned(case)
     (a, smalls, _, rows), want, start, q = reference(name)   # (the exactness condition is asserted inside, on the reference alone)
     print(f"{name}: range quantity {X.headroom(q, case.arith_kind)}")
-    got = run_case(case, a, smalls, start, rows)
+    got = (run_view_case if E.has_views(case) else run_case)(case, a, smalls, start, rows)
     assert got.shape == want.shape
     assert np.array_equal(got, want.astype(got.dtype)), (name, int(np.count_nonzero(got != want)), "of", got.size, "values differ")
 
