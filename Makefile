@@ -6,10 +6,10 @@ LIB := artensor_amd/libartn_hip.so
 
 all: $(LIB)
 
-# Twenty-three objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit),
-# artn_born.hip, artn_rdm.hip, artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_krylov.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip, artn_bitperm.hip, and the eleven few-line sources under units/, each of which defines one artn_launch_*() and so
+# Twenty-four objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit),
+# artn_born.hip, artn_rdm.hip, artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_mgate.hip, artn_cgate.hip, artn_krylov.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip, artn_bitperm.hip, and the eleven few-line sources under units/, each of which defines one artn_launch_*() and so
 # emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by all of them).  Two headers
-# belong to no single object: artn_state_host.h (born, rdm, pauli, gates, wgate, cgate, measure, channel, diag, bitperm) and artn_block_kernel.h (pauli, gates):
+# belong to no single object: artn_state_host.h (born, rdm, pauli, gates, wgate, mgate, cgate, measure, channel, diag, bitperm) and artn_block_kernel.h (pauli, gates):
 # `make -j8` builds in about a minute and a half instead of four.
 HOST_HDRS := $(CSRC)/artn_host.h include/artn.h
 # (the operations on a dense amplitude array: shared host checks, and the block skeleton of the four run kernels)
@@ -26,6 +26,7 @@ PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pa
               $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
 GATES_SRCS := $(CSRC)/artn_gates.hip $(CSRC)/artn_gates_kernel.h $(CSRC)/artn_gates_adjoint_kernel.h $(PAULI_SRCS)
 WGATE_SRCS := $(CSRC)/artn_wgate.hip $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
+MGATE_SRCS := $(CSRC)/artn_mgate.hip $(CSRC)/artn_mgate_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
 CGATE_SRCS := $(CSRC)/artn_cgate.hip $(CSRC)/artn_cgate_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
 KRYLOV_SRCS := $(CSRC)/artn_krylov.hip $(CSRC)/artn_krylov_kernel.h $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
 MEASURE_SRCS := $(CSRC)/artn_measure.hip $(CSRC)/artn_measure_kernel.h $(STATE_HDRS)
@@ -33,7 +34,7 @@ CHANNEL_SRCS := $(CSRC)/artn_channel.hip $(CSRC)/artn_channel_kernel.h $(CSRC)/a
 DIAG_SRCS := $(CSRC)/artn_diag.hip $(CSRC)/artn_diag_kernel.h $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
 BITPERM_SRCS := $(CSRC)/artn_bitperm.hip $(CSRC)/artn_bitperm_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
 # (the single-translation-unit builds below: artn_unity.hip includes every unit source)
-SRCS := $(CSRC)/artn_unity.hip $(CSRC)/artn_api.hip $(wildcard $(CSRC)/units/*.hip) $(HDRS) $(LAUNCH_HDRS) $(MAIN_HDRS) $(BORN_SRCS) $(RDM_SRCS) $(PAULI_SRCS) $(GATES_SRCS) $(WGATE_SRCS) $(CGATE_SRCS) $(KRYLOV_SRCS) $(MEASURE_SRCS) $(CHANNEL_SRCS) $(DIAG_SRCS) $(BITPERM_SRCS)
+SRCS := $(CSRC)/artn_unity.hip $(CSRC)/artn_api.hip $(wildcard $(CSRC)/units/*.hip) $(HDRS) $(LAUNCH_HDRS) $(MAIN_HDRS) $(BORN_SRCS) $(RDM_SRCS) $(PAULI_SRCS) $(GATES_SRCS) $(WGATE_SRCS) $(MGATE_SRCS) $(CGATE_SRCS) $(KRYLOV_SRCS) $(MEASURE_SRCS) $(CHANNEL_SRCS) $(DIAG_SRCS) $(BITPERM_SRCS)
 OBJDIR := build/obj
 # The product library carries what the default planner can select.  `make dev` (DEV=1) adds the development-only pieces:
 # every ARTN_* planner switch of the A/B measurements in DESIGN.md (-DARTN_DEV_SWITCHES), three-step fusion (artn_k_bits3 /
@@ -48,7 +49,7 @@ DEVOBJS :=
 endif
 # (the longest translation units first: make -j starts its jobs in this order)
 OBJS := $(foreach k,6 5,$(OBJDIR)/bits_k$(k)h0.o $(OBJDIR)/bits_k$(k)h1.o) $(OBJDIR)/main.o $(OBJDIR)/bits_k4.o $(OBJDIR)/bits_k3.o \
-        $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(OBJDIR)/born.o $(OBJDIR)/rdm.o $(OBJDIR)/pauli.o $(OBJDIR)/gates.o $(OBJDIR)/wgate.o $(OBJDIR)/cgate.o $(OBJDIR)/krylov.o $(OBJDIR)/measure.o $(OBJDIR)/channel.o $(OBJDIR)/diag.o $(OBJDIR)/bitperm.o $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
+        $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(OBJDIR)/born.o $(OBJDIR)/rdm.o $(OBJDIR)/pauli.o $(OBJDIR)/gates.o $(OBJDIR)/wgate.o $(OBJDIR)/mgate.o $(OBJDIR)/cgate.o $(OBJDIR)/krylov.o $(OBJDIR)/measure.o $(OBJDIR)/channel.o $(OBJDIR)/diag.o $(OBJDIR)/bitperm.o $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
 FLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Iinclude -I$(CSRC) $(DEVFLAGS)
 
 define COMPILE
@@ -66,6 +67,8 @@ $(OBJDIR)/pauli.o: $(PAULI_SRCS)
 $(OBJDIR)/gates.o: $(GATES_SRCS)
 	$(COMPILE)
 $(OBJDIR)/wgate.o: $(WGATE_SRCS)
+	$(COMPILE)
+$(OBJDIR)/mgate.o: $(MGATE_SRCS)
 	$(COMPILE)
 $(OBJDIR)/cgate.o: $(CGATE_SRCS)
 	$(COMPILE)

@@ -112,6 +112,15 @@ from .wide_gates import (  # noqa: F401
     fuse_gates,
     wide_gate_info,
 )
+from . import matrix_gates  # noqa: F401
+from .matrix_gates import (  # noqa: F401
+    BlockCircuit,
+    MatrixGate,
+    apply_blocks_,
+    apply_matrix_gate_,
+    fuse_gates_wide,
+    matrix_gate_info,
+)
 from . import controlled  # noqa: F401
 from .controlled import (  # noqa: F401
     ControlledGate,

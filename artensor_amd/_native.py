@@ -212,6 +212,9 @@ class ArtnWgateInfo(ctypes.Structure):
 WGATE_MAX_K = 5
 WGATE_TILE_BITS = {ARTN_C64: 12, ARTN_C128: 11}
 WGATE_TABLE_HEADER_BYTES = 480
+ArtnMgateInfo = ArtnWgateInfo                                  # (include/artn.h: the same fields)
+MGATE_MIN_K, MGATE_MAX_K = 3, 7
+MGATE_TABLE_HEADER_BYTES = 544
 
 
 class ArtnCgateInfo(ctypes.Structure):
@@ -463,6 +466,13 @@ _EXPORTS = {
     "artn_wgate_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int64]),
     "artn_wgate_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: one dense gate on three to seven qubits on the f64 matrix cores (has("artn_mgate_apply"))
+    "artn_mgate_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.POINTER(ArtnMgateInfo), ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_mgate_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_int64]),
+    "artn_mgate_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     # additive to ABI 9 as well: one dense gate under any number of controls and a device-resident condition (has("artn_cgate_apply"))
     "artn_cgate_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,

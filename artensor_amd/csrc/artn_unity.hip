@@ -23,6 +23,7 @@
 #include "artn_pauli.hip" // (artn_pauli_kernel.h, artn_pauli_apply_kernel.h, artn_pauli_evolve_kernel.h, artn_pauli_adjoint_kernel.h)
 #include "artn_gates.hip" // (artn_gates_kernel.h, artn_gates_adjoint_kernel.h)
 #include "artn_wgate.hip" // (artn_wgate_kernel.h)
+#include "artn_mgate.hip" // (artn_mgate_kernel.h)
 #include "artn_cgate.hip" // (artn_cgate_kernel.h)
 #include "artn_krylov.hip" // (artn_krylov_kernel.h)
 #include "artn_measure.hip" // (artn_measure_kernel.h)

@@ -154,15 +154,20 @@ def fuse_gates(gates, max_width):
     kron-embedded blocks in their original order, formed in complex128; its dims are in ascending order.  Any other gate starts
     a block of its own (a gate wider than max_width, up to 5, stays as it is).  This changes rounding (fewer, different
     matrices), so nothing calls it implicitly; the result is deterministic."""
-    if isinstance(max_width, bool) or not isinstance(max_width, (int, np.integer)) or not 2 <= int(max_width) <= _native.WGATE_MAX_K:
-        raise ValueError(f"fuse_gates: max_width must be an integer in 2..{_native.WGATE_MAX_K}, got {max_width!r}")
+    return _fuse(gates, max_width, _native.WGATE_MAX_K, "fuse_gates")
+
+
+def _fuse(gates, max_width, top, who):
+    """fuse_gates for gates and blocks of up to `top` qubits (matrix_gates.fuse_gates_wide lifts the limit to 7)."""
+    if isinstance(max_width, bool) or not isinstance(max_width, (int, np.integer)) or not 2 <= int(max_width) <= top:
+        raise ValueError(f"{who}: max_width must be an integer in 2..{top}, got {max_width!r}")
     max_width = int(max_width)
     out, last = [], {}                                         # out: [matrix, qubits] or None (joined); last[q]: index into out
     for g, gate in enumerate(gates):
         k = _width(gate, g)
         dims = (int(gate[1]),) if isinstance(gate[1], (int, np.integer)) else tuple(int(x) for x in gate[1])
-        if not 1 <= k <= _native.WGATE_MAX_K or len(set(dims)) != k:
-            raise ValueError(f"gate {g}: one to {_native.WGATE_MAX_K} distinct dims expected, got {dims}")
+        if not 1 <= k <= top or len(set(dims)) != k:
+            raise ValueError(f"gate {g}: one to {top} distinct dims expected, got {dims}")
         m = _matrix(gate[0], k, f"gate {g}")
         before = sorted({last[q] for q in dims if q in last})
         is_open = all(all(last[q] == b for q in out[b][1]) for b in before)

@@ -781,6 +781,72 @@ int artn_wgate_pack(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, c
 int artn_wgate_apply(const ArtnMarginalDesc *d, void *a, int32_t k, const int32_t *dims, const void *table, int64_t table_bytes,
                      void *stream);
 
+/*
+ * ONE dense gate on three to seven qubits, in place, in one launch, on the float64 MATRIX CORES (additive to ABI 9:
+ * has("artn_mgate_apply")).  A family beside artn_wgate_*, with an arithmetic contract of its own; the three calls mirror the
+ * three artn_wgate_* calls in arguments, error codes and error texts (the wording "matrix gates take ...", and k outside 3..7 is
+ * ARTN_E_UNSUPPORTED "matrix gates act on three to seven dimensions").  mat, dims and the convention (the FIRST listed dimension
+ * is the most significant digit) are those of artn_wgate_query.
+ *
+ * PLAN: that of artn_wgate_query, unchanged and for k up to 7 -- tiles of 2^TB elements (TB = ARTN_WGATE_TILE_BITS_C64 / _C128, or
+ * the whole state), the tile bits the k targets and the lowest other bits, segments, the tile base with a 0 inserted at every high
+ * target, the LDS image ((c << GB) | g) ^ sw(c) with GB = TB - k, and the column tables.  At k = 7 a full tile has 2^5 (complex64)
+ * or 2^4 (complex128) groups, so a segment is never below 256 bytes.
+ *
+ * KERNEL: 256 threads = 4 wavefronts grid-stride over the tiles.  Per tile: (1) 16-byte loads into the LDS image; (2) the complex
+ * GEMM Y[2^k x G] = U X[2^k x G] (G = 2^GB groups) as a real one on v_mfma_f64_16x16x4_f64; (3) after a barrier every output
+ * component is rounded once to the dtype and written to its place in LDS; (4) 16-byte stores.  One instruction multiplies a ROW
+ * BLOCK rb (output rows 8 rb .. 8 rb + 7) and a STEP s (input rows 2 s and 2 s + 1) with a COLUMN BLOCK cb (groups 16 cb ..
+ * 16 cb + 15).  A state with fewer than 16 groups reads group (g mod G) for the missing columns and does not write them.
+ *
+ * ARITHMETIC.  The component (row r, re or im) of group g is a float64 sum of its 2 * 2^k real products: the accumulator starts
+ * at +0.0; the steps come in the order s = 0 .. 2^(k-1) - 1; step s adds, in the order the instruction adds its four products,
+ * U[r][2s] x[2s], U[r][2s+1] x[2s+1] with (Re U Re x, -Im U Im x) for the real part and (Im U Re x, Re U Im x) for the imaginary
+ * part.  One rounding of each component to the dtype.  No atomics: results are bit-identical from run to run and between an eager
+ * call and a graph replay.  Where every product and every partial sum is exactly representable (integers below 2^53; below 2^24
+ * after the final rounding for complex64) the result is exact whatever the order, so on finite data the identity and signed
+ * permutations reproduce their input values under ==.  UNLIKE artn_wgate_apply, zero coefficients are multiplied: the sign of a
+ * zero is not preserved, and a non-finite element may make every output of its group non-finite.  The result is not bit for bit
+ * artn_wgate_apply's; every component agrees with the exact one within
+ *     2^-24 |exact| (complex64: the one rounding) + 4 * 2^k * 2^-53 * sum_c (|Re u| + |Im u|)(|Re x| + |Im x|)
+ * (a float64 sum of 2^(k+1) products in any order, with a factor 2 of slack).
+ *
+ * TABLE (what artn_mgate_pack writes and the kernel reads; 8-byte little-endian fields): ArtnMgateTable, 544 bytes, then the matrix
+ * as float64 in FRAGMENT ORDER, 16 * 4^k bytes: the double at index
+ *     ((((rb * 2^(k-1) + s) * 8 + n) * 2 + h) * 2 + c)        rb < 2^k / 8, s < 2^(k-1), n < 8, h < 2, c < 2
+ * is Re (c = 0) or Im (c = 1) of U[8 rb + n][2 s + h].  Lane l of a wavefront (j = l & 15, q = l >> 4) takes for (rb, s) the
+ * entry n = j >> 1, h = q >> 1, c = (j ^ q) & 1, with its sign flipped when j is even and q is odd.  table_bytes = 544 + 16 * 4^k
+ * (256 KiB + 544 at k = 7).
+ */
+#define ARTN_MGATE_MIN_K 3
+#define ARTN_MGATE_MAX_K 7
+typedef struct ArtnMgateTable {
+  uint64_t k, tile_bits, n_tiles, segment;
+  uint64_t flags;      /* ARTN_GATE_DIAGONAL                                                                          */
+  uint64_t group_bits; /* tile_bits - k                                                                                */
+  uint64_t n_high;     /* tile bits at or above log2(segment): all targets                                             */
+  uint64_t reserved;
+  uint64_t target_bit[ARTN_MGATE_MAX_K]; /* the memory bits of the targets in the order listed                         */
+  uint64_t target_pos[ARTN_MGATE_MAX_K]; /* their tile-local positions, same order                                     */
+  uint64_t high_bit[ARTN_MGATE_MAX_K];   /* the high targets' memory bits, ascending (0 beyond n_high)                  */
+  uint64_t swizzle[ARTN_MGATE_MAX_K];    /* per ROW bit i (the i-th target from the last listed one), below 2^group_bits */
+  uint64_t mem_col[16];                  /* per tile-local bit j: 1 << its memory bit (0 beyond tile_bits)               */
+  uint64_t lds_col[16];                  /* per tile-local bit j: what it contributes (XOR) to the LDS index             */
+} ArtnMgateTable;
+typedef ArtnWgateInfo ArtnMgateInfo; /* the same fields; table_bytes = 544 + 16 * 4^k */
+/* Host-only: validates and plans.  target_bits (k entries, the order listed) and tile_bits (info->tile_bits entries, ascending;
+ * room for 12) may be NULL. */
+int artn_mgate_query(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const double *mat, ArtnMgateInfo *info,
+                     int32_t *target_bits, int32_t *tile_bits);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_mgate_pack(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, const double *mat, void *table, int64_t table_bytes);
+/* The gate on `a`, in place: ONE launch on `stream`.  `table` is DEVICE memory holding what artn_mgate_pack wrote for the same
+ * descriptor, k and dims (8-byte aligned; a table_bytes below the query's is ARTN_E_INVALID; a table packed for another k makes
+ * the launch return without touching memory); `a` is 16-byte aligned (ARTN_E_UNSUPPORTED otherwise).  No allocation, copy or
+ * synchronisation.  ARTN_E_NODEVICE without a device. */
+int artn_mgate_apply(const ArtnMarginalDesc *d, void *a, int32_t k, const int32_t *dims, const void *table, int64_t table_bytes,
+                     void *stream);
+
 /* ---- the vector algebra of Krylov drivers (additive to ABI 9: has("artn_krylov_combine")) ------------------------------------
  * Vectors are complex64 or complex128 arrays of n elements (1 <= n <= 2^40) in DEVICE memory, 16-byte aligned; every vector of a
  * call has the same dtype and the same dense layout, so the kernels work on the flat memory range.  float64 arithmetic in an
