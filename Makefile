@@ -6,35 +6,15 @@ LIB := artensor_amd/libartn_hip.so
 
 all: $(LIB)
 
-# Twenty-four objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit),
-# artn_born.hip, artn_rdm.hip, artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_mgate.hip, artn_cgate.hip, artn_krylov.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip, artn_bitperm.hip, and the eleven few-line sources under units/, each of which defines one artn_launch_*() and so
-# emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by all of them).  Two headers
-# belong to no single object: artn_state_host.h (born, rdm, pauli, gates, wgate, mgate, cgate, measure, channel, diag, bitperm) and artn_block_kernel.h (pauli, gates):
-# `make -j8` builds in about a minute and a half instead of four.
-HOST_HDRS := $(CSRC)/artn_host.h include/artn.h
-# (the operations on a dense amplitude array: shared host checks, and the block skeleton of the four run kernels)
-STATE_HDRS := $(CSRC)/artn_state_host.h $(HOST_HDRS)
-HDRS := $(HOST_HDRS) $(CSRC)/artn_kernels.hip $(CSRC)/artn_wide_kernel.h $(CSRC)/artn_plan.h $(CSRC)/artn_xgemm_plan.h
-LAUNCH_HDRS := $(CSRC)/artn_launch_bits.h $(CSRC)/artn_launch_bits128.h $(CSRC)/artn_launch_bits3.h \
-               $(CSRC)/artn_bits128_kernel.h $(CSRC)/artn_bits3_kernel.h
-MAIN_HDRS := $(CSRC)/artn_gemm_kernel.h $(CSRC)/artn_gemm128_kernel.h $(CSRC)/artn_pgemm_kernel.h $(CSRC)/artn_xgemm_kernel.h \
-             $(CSRC)/artn_xgemm128_kernel.h $(CSRC)/artn_xrow_kernel.h $(CSRC)/artn_xgemm_pc_kernel.h
-BORN_SRCS := $(CSRC)/artn_born.hip $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
-RDM_SRCS := $(CSRC)/artn_rdm.hip $(CSRC)/artn_rdm_kernel.h $(STATE_HDRS)
-PAULI_SRCS := $(CSRC)/artn_pauli.hip $(CSRC)/artn_pauli_kernel.h $(CSRC)/artn_pauli_apply_kernel.h $(CSRC)/artn_pauli_evolve_kernel.h \
-              $(CSRC)/artn_pauli_adjoint_kernel.h $(CSRC)/artn_block_kernel.h \
-              $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
-GATES_SRCS := $(CSRC)/artn_gates.hip $(CSRC)/artn_gates_kernel.h $(CSRC)/artn_gates_adjoint_kernel.h $(PAULI_SRCS)
-WGATE_SRCS := $(CSRC)/artn_wgate.hip $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
-MGATE_SRCS := $(CSRC)/artn_mgate.hip $(CSRC)/artn_mgate_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
-CGATE_SRCS := $(CSRC)/artn_cgate.hip $(CSRC)/artn_cgate_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
-KRYLOV_SRCS := $(CSRC)/artn_krylov.hip $(CSRC)/artn_krylov_kernel.h $(CSRC)/artn_born_kernel.h $(HOST_HDRS)
-MEASURE_SRCS := $(CSRC)/artn_measure.hip $(CSRC)/artn_measure_kernel.h $(STATE_HDRS)
-CHANNEL_SRCS := $(CSRC)/artn_channel.hip $(CSRC)/artn_channel_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
-DIAG_SRCS := $(CSRC)/artn_diag.hip $(CSRC)/artn_diag_kernel.h $(CSRC)/artn_born_kernel.h $(STATE_HDRS)
-BITPERM_SRCS := $(CSRC)/artn_bitperm.hip $(CSRC)/artn_bitperm_kernel.h $(CSRC)/artn_wgate_kernel.h $(CSRC)/artn_gates_kernel.h $(PAULI_SRCS)
+# Twenty-four objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit), one
+# artn_<family>.hip per word of FAMILIES, and the eleven few-line sources under units/, each of which defines one
+# artn_launch_*() and so emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by
+# all of them).  `make -j8` builds in about a minute and a half instead of four.  What an object depends on beyond its source
+# is what the compiler saw it include (-MMD -MP: build/obj/<object>.d, read back below); no list of headers is kept by hand.
+# A new family is one word here and one #include in artn_unity.hip.
+FAMILIES := born rdm pauli gates wgate mgate cgate krylov measure channel diag bitperm
 # (the single-translation-unit builds below: artn_unity.hip includes every unit source)
-SRCS := $(CSRC)/artn_unity.hip $(CSRC)/artn_api.hip $(wildcard $(CSRC)/units/*.hip) $(HDRS) $(LAUNCH_HDRS) $(MAIN_HDRS) $(BORN_SRCS) $(RDM_SRCS) $(PAULI_SRCS) $(GATES_SRCS) $(WGATE_SRCS) $(MGATE_SRCS) $(CGATE_SRCS) $(KRYLOV_SRCS) $(MEASURE_SRCS) $(CHANNEL_SRCS) $(DIAG_SRCS) $(BITPERM_SRCS)
+SRCS := $(CSRC)/artn_unity.hip $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/units/*.hip) include/artn.h
 OBJDIR := build/obj
 # The product library carries what the default planner can select.  `make dev` (DEV=1) adds the development-only pieces:
 # every ARTN_* planner switch of the A/B measurements in DESIGN.md (-DARTN_DEV_SWITCHES), three-step fusion (artn_k_bits3 /
@@ -49,41 +29,20 @@ DEVOBJS :=
 endif
 # (the longest translation units first: make -j starts its jobs in this order)
 OBJS := $(foreach k,6 5,$(OBJDIR)/bits_k$(k)h0.o $(OBJDIR)/bits_k$(k)h1.o) $(OBJDIR)/main.o $(OBJDIR)/bits_k4.o $(OBJDIR)/bits_k3.o \
-        $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(OBJDIR)/born.o $(OBJDIR)/rdm.o $(OBJDIR)/pauli.o $(OBJDIR)/gates.o $(OBJDIR)/wgate.o $(OBJDIR)/mgate.o $(OBJDIR)/cgate.o $(OBJDIR)/krylov.o $(OBJDIR)/measure.o $(OBJDIR)/channel.o $(OBJDIR)/diag.o $(OBJDIR)/bitperm.o $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
+        $(OBJDIR)/b128.o $(OBJDIR)/b128a.o $(OBJDIR)/wide.o $(FAMILIES:%=$(OBJDIR)/%.o) $(OBJDIR)/bits_k2.o $(OBJDIR)/bits_k1.o $(DEVOBJS)
 FLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Iinclude -I$(CSRC) $(DEVFLAGS)
 
 define COMPILE
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(FLAGS) -c $< -o $@
+	$(HIPCC) $(FLAGS) -MMD -MP -c $< -o $@
 endef
-$(OBJDIR)/main.o: $(CSRC)/artn_api.hip $(HDRS) $(MAIN_HDRS)
+$(OBJDIR)/main.o: $(CSRC)/artn_api.hip
 	$(COMPILE)
-$(OBJDIR)/born.o: $(BORN_SRCS)
+$(OBJDIR)/%.o: $(CSRC)/artn_%.hip
 	$(COMPILE)
-$(OBJDIR)/rdm.o: $(RDM_SRCS)
+$(OBJDIR)/%.o: $(CSRC)/units/%.hip
 	$(COMPILE)
-$(OBJDIR)/pauli.o: $(PAULI_SRCS)
-	$(COMPILE)
-$(OBJDIR)/gates.o: $(GATES_SRCS)
-	$(COMPILE)
-$(OBJDIR)/wgate.o: $(WGATE_SRCS)
-	$(COMPILE)
-$(OBJDIR)/mgate.o: $(MGATE_SRCS)
-	$(COMPILE)
-$(OBJDIR)/cgate.o: $(CGATE_SRCS)
-	$(COMPILE)
-$(OBJDIR)/krylov.o: $(KRYLOV_SRCS)
-	$(COMPILE)
-$(OBJDIR)/measure.o: $(MEASURE_SRCS)
-	$(COMPILE)
-$(OBJDIR)/channel.o: $(CHANNEL_SRCS)
-	$(COMPILE)
-$(OBJDIR)/diag.o: $(DIAG_SRCS)
-	$(COMPILE)
-$(OBJDIR)/bitperm.o: $(BITPERM_SRCS)
-	$(COMPILE)
-$(OBJDIR)/%.o: $(CSRC)/units/%.hip $(HDRS) $(LAUNCH_HDRS)
-	$(COMPILE)
+-include $(OBJS:.o=.d)
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared $(OBJS) -o $@
 

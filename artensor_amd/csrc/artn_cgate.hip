@@ -80,7 +80,7 @@ static void cgate_launch(const CgatePlan &cp, T *a, const void *table, const voi
   const long long m = (long long)mask, v = (long long)value;
   const dim3 grid((unsigned)std::min<int64_t>(cp.info.n_tiles, ARTN_WGATE_MAX_GRID)), block(ARTN_BORN_THREADS);
   const size_t lds = (size_t)cp.info.lds_bytes;
-  state_with_k(cp.t, [&](auto k) {
+  state_with_k<1, ARTN_WGATE_MAX_K>(cp.t, [&](auto k) {
     hipLaunchKernelGGL((artn_k_cgate<T, decltype(k)::value>), grid, block, lds, st, a, tab, cnd, m, v);
   });
 }

@@ -83,7 +83,7 @@ static void channel_launch(const ChannelPlan &cp, T *a, const void *table, const
   const dim3 grid((unsigned)std::min<int64_t>(cp.info.n_tiles, ARTN_WGATE_MAX_GRID)), block(ARTN_BORN_THREADS);
   const size_t lds = (size_t)cp.info.lds_bytes;
   const int m = cp.m;
-  state_with_k(cp.t, [&](auto k) {
+  state_with_k<1, ARTN_WGATE_MAX_K>(cp.t, [&](auto k) {
     hipLaunchKernelGGL((artn_k_channel<T, decltype(k)::value>), grid, block, lds, st, a, tab, rec, m);
   });
 }
@@ -119,11 +119,8 @@ int artn_channel_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims,
   if (int rc = state_table_aligned(table, "artn_channel_pack")) return rc;
   ArtnChannelTable ct = {};
   ArtnWgateTable &g = ct.gate;
-  const int rows = 1 << t, gb = cp.tb - t;
-  g.k = (uint64_t)t, g.tile_bits = (uint64_t)cp.tb, g.n_tiles = (uint64_t)cp.info.n_tiles, g.segment = (uint64_t)cp.info.segment;
-  g.group_bits = (uint64_t)gb, g.n_high = (uint64_t)(cp.tb - cp.seg_bits);
-  for (int j = cp.seg_bits; j < cp.tb; ++j) g.high_bit[j - cp.seg_bits] = (uint64_t)cp.tile[j];
-  state_tile_cols(cp, g.mem_col, g.lds_col, g.target_bit, g.target_pos, g.swizzle);
+  const int rows = 1 << t;
+  state_tile_header(cp, t, false, g); // (the flag "diagonal": below, once every operator has been scanned)
   ct.m = (uint64_t)m, ct.form = (uint64_t)form, ct.weight_doubles = (uint64_t)wd;
   // per operator: the block mask, "diagonal" and "exactly the identity"
   ArtnChannelOp *ops = (ArtnChannelOp *)((ArtnChannelTable *)table + 1);

@@ -1,8 +1,11 @@
 // artn_state_host.h -- host plumbing shared by the operations on a dense amplitude array (artn_born.hip, artn_rdm.hip,
-// artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip, artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the max_rank rule and the
-// rank dispatch of the run kernels, the matrix scan, the argument checks of the pack / apply entries, the parts of a packed
-// table, and the plan, the column packer and the K dispatch of the tile kernels (wide gates, controlled gates, channels).  Codes and texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording
-// (`who`: "gate circuits take", ...) and its own precedence between the errors, so the pieces are separate functions.
+// artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_mgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip,
+// artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the max_rank rule and the rank dispatch of the run
+// kernels, the matrix scan, the argument checks of the pack / apply entries, the parts of a packed table, the plan, the
+// column packer, the table header and the K dispatch of the tile kernels (wide gates, matrix gates, controlled gates,
+// channels).  The whole host half of the two dense-gate families is artn_dense_gate_host.h, on top of this.  Codes and
+// texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording (`who`: "gate
+// circuits take", ...) and its own precedence between the errors, so the pieces are separate functions.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -147,7 +150,7 @@ static void state_table_parts(Void *table, size_t n_runs, Run *&runs, Rec *&recs
   recs = (Rec *)(runs + n_runs);
 }
 
-// ---- the tile kernels: artn_k_wgate, artn_k_cgate, artn_k_channel (include/artn.h: PLAN of artn_wgate_query) ----------------
+// ---- the tile kernels: artn_k_wgate, artn_k_mgate, artn_k_cgate, artn_k_channel (include/artn.h: PLAN of artn_wgate_query) ----
 
 // One listed dimension of a gate or channel (`what`: "gates", "channels"): in range, of extent 2, not among `seen`, the
 // dimensions listed before it -- the n_targets targets first, so a control that repeats one of those gets its own text.
@@ -233,11 +236,20 @@ static uint64_t state_block_mask(const double *mat, int rows) {
   return mask;
 }
 
-// f(std::integral_constant<int, K>) for the run-time k = 1 .. ARTN_WGATE_MAX_K; the plans admit no other k
-template <int K = 1, typename F>
+// f(std::integral_constant<int, K>) for the run-time k = LO .. HI; the plans admit no other k
+template <int LO, int HI, typename F>
 static void state_with_k(int k, F &&f) {
-  if constexpr (K <= ARTN_WGATE_MAX_K) {
-    if (k == K) f(std::integral_constant<int, K>());
-    else state_with_k<K + 1>(k, f);
+  if constexpr (LO <= HI) {
+    if (k == LO) f(std::integral_constant<int, LO>());
+    else state_with_k<LO + 1, HI>(k, f);
   }
+}
+
+// the fields every tile table begins with (ArtnWgateTable, ArtnMgateTable, the `gate` of ArtnChannelTable), from the plan
+template <typename Table>
+static void state_tile_header(const TilePlan &tp, int k, bool diagonal, Table &t) {
+  t.k = (uint64_t)k, t.tile_bits = (uint64_t)tp.tb, t.n_tiles = (uint64_t)tp.n_tiles, t.segment = (uint64_t)tp.segment;
+  t.flags = diagonal ? ARTN_GATE_DIAGONAL : 0, t.group_bits = (uint64_t)(tp.tb - k), t.n_high = (uint64_t)(tp.tb - tp.seg_bits);
+  for (int j = tp.seg_bits; j < tp.tb; ++j) t.high_bit[j - tp.seg_bits] = (uint64_t)tp.tile[j]; // (all targets: include/artn.h)
+  state_tile_cols(tp, t.mem_col, t.lds_col, t.target_bit, t.target_pos, t.swizzle);
 }

@@ -18,27 +18,81 @@ import numpy as np
 import torch
 
 from . import _native
-from ._state import _Prebuilt, _checked, _desc, _dims, _dtype_code, _interleaved, _packed, _ptr
+from ._state import _Prebuilt, _checked, _desc, _dims, _dtype_code, _interleaved, _lib, _packed, _ptr
 from .gates import GateCircuit, _matrix
 
 __all__ = ["apply_wide_gate_", "WideGate", "wide_gate_info", "FusedCircuit", "apply_circuit_", "fuse_gates"]
 
 
-def _split_gate(matrix, dims, n_dims, what):
-    """(k, int32 dims [k], float64 mat [2 * 4^k]); a k the library does not take keeps a zero matrix, so that the library refuses it."""
-    dims = _dims(dims, n_dims)
-    k = int(dims.shape[0])
-    if not 1 <= k <= _native.WGATE_MAX_K:
-        return k, (dims if k else np.zeros(1, dtype=np.int32)), np.zeros(2, dtype=np.float64)
-    return k, dims, _interleaved(_matrix(matrix, k, what))
+class _DenseGate(_Prebuilt):
+    """One gate (matrix, dims) of a dense-gate family, for tensors of one layout: validates, plans, packs the table and copies it
+    to `device` once; g(amps) then updates amps IN PLACE with one launch and returns it.  A family (WideGate here, MatrixGate in
+    matrix_gates.py) declares `_prefix` (its entries are <prefix>_query, _pack, _apply), `_k_min` and `_k_max`, `_name` (the
+    module-qualified name in messages) and `_family`: None, or what the refusal of a library built before the family calls it."""
+
+    _prefix = _name = _family = None
+    _k_min = _k_max = 0
+
+    def __init__(self, shape, strides, dtype, matrix, dims, device):
+        self._bind(shape, strides, dtype, device)
+        self.k, self._dims, mat = self._split(matrix, dims, len(self.shape), type(self).__name__)
+        self._d = _desc(self.shape, self.strides, dtype)
+        table, info = self._pack(self._d, self.k, self._dims, mat)
+        self.table_bytes, self.tile_bits, self.n_tiles = info.table_bytes, info.tile_bits, info.n_tiles
+        self._upload(table)
+
+    def __call__(self, amps):
+        self._check(amps, self._name)
+        with torch.cuda.device(amps.device):
+            _native.check(getattr(_native.lib(), self._prefix + "_apply")(
+                ctypes.byref(self._d), amps.data_ptr(), self.k, _ptr(self._dims), self._table.data_ptr(), self.table_bytes,
+                _native.current_stream_ptr(amps.device)))
+        return amps
+
+    @classmethod
+    def _split(cls, matrix, dims, n_dims, what):
+        """(k, int32 dims [k], float64 mat [2 * 4^k]); a k the library does not take keeps a zero matrix, so that the library refuses it."""
+        dims = _dims(dims, n_dims)
+        k = int(dims.shape[0])
+        if not cls._k_min <= k <= cls._k_max:
+            return k, (dims if k else np.zeros(1, dtype=np.int32)), np.zeros(2, dtype=np.float64)
+        return k, dims, _interleaved(_matrix(matrix, k, what))
+
+    @classmethod
+    def _query(cls, d, k, dims, mat, arrays=False, what=None):
+        lib = _lib(cls._prefix + "_apply", cls._family, what or cls._name.split(".")[0]) if cls._family else _native.lib()
+        info = _native.ArtnWgateInfo()
+        target, tile = np.full(cls._k_max, -1, dtype=np.int32), np.full(12, -1, dtype=np.int32)
+        _native.check(getattr(lib, cls._prefix + "_query")(ctypes.byref(d), k, _ptr(dims), _ptr(mat), ctypes.byref(info),
+                                                           _ptr(target) if arrays else None, _ptr(tile) if arrays else None))
+        return info, target, tile
+
+    @classmethod
+    def _info(cls, shape, strides, matrix, dims, dtype, what):
+        _dtype_code(dtype, what)
+        k, dims, mat = cls._split(matrix, dims, len(shape), what)
+        info, target, tile = cls._query(_desc(shape, strides, dtype), k, dims, mat, arrays=True, what=what)
+        return {"k": info.k, "target_bits": tuple(int(b) for b in target[:k]), "tile_bits": [int(b) for b in tile[:info.tile_bits]],
+                "tb": info.tile_bits, "n_tiles": info.n_tiles, "segment": info.segment, "lds_bytes": info.lds_bytes,
+                "table_bytes": info.table_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written,
+                "diagonal": bool(info.diagonal)}
+
+    @classmethod
+    def _pack(cls, d, k, dims, mat):
+        """The gate's table (include/artn.h) as a uint8 numpy array."""
+        return _packed(cls._query(d, k, dims, mat)[0],
+                       lambda *table: getattr(_native.lib(), cls._prefix + "_pack")(ctypes.byref(d), k, _ptr(dims), _ptr(mat), *table))
 
 
-def _wgate_query(d, k, dims, mat, arrays=False):
-    info = _native.ArtnWgateInfo()
-    target, tile = np.full(_native.WGATE_MAX_K, -1, dtype=np.int32), np.full(12, -1, dtype=np.int32)
-    _native.check(_native.lib().artn_wgate_query(ctypes.byref(d), k, _ptr(dims), _ptr(mat), ctypes.byref(info),
-                                                 _ptr(target) if arrays else None, _ptr(tile) if arrays else None))
-    return info, target, tile
+class WideGate(_DenseGate):
+    """One gate (matrix, dims), k = len(dims) in 1..5, for tensors of one layout.  Validates, plans, packs the table and copies it
+    to `device` once; g(amps) then updates amps IN PLACE with one launch and returns it."""
+
+    _prefix, _name = "artn_wgate", "wide_gates.WideGate"
+    _k_min, _k_max = 1, _native.WGATE_MAX_K
+
+
+_split_gate, _wgate_query, _wgate_pack = WideGate._split, WideGate._query, WideGate._pack
 
 
 def wide_gate_info(shape, strides, matrix, dims, dtype=torch.complex64):
@@ -46,40 +100,7 @@ def wide_gate_info(shape, strides, matrix, dims, dtype=torch.complex64):
     targets and the lowest other memory bits), tb (their number: 12 for complex64, 11 for complex128, or log2 of a smaller
     state), n_tiles, segment (elements of a contiguous piece of a tile), lds_bytes, table_bytes, bytes_read = bytes_written =
     bytes of the state, diagonal."""
-    _dtype_code(dtype, "wide_gate_info")
-    k, dims, mat = _split_gate(matrix, dims, len(shape), "wide_gate_info")
-    info, target, tile = _wgate_query(_desc(shape, strides, dtype), k, dims, mat, arrays=True)
-    return {"k": info.k, "target_bits": tuple(int(b) for b in target[:k]), "tile_bits": [int(b) for b in tile[:info.tile_bits]],
-            "tb": info.tile_bits, "n_tiles": info.n_tiles, "segment": info.segment, "lds_bytes": info.lds_bytes,
-            "table_bytes": info.table_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written,
-            "diagonal": bool(info.diagonal)}
-
-
-def _wgate_pack(d, k, dims, mat):
-    """The gate's table (include/artn.h) as a uint8 numpy array."""
-    return _packed(_wgate_query(d, k, dims, mat)[0],
-                   lambda *table: _native.lib().artn_wgate_pack(ctypes.byref(d), k, _ptr(dims), _ptr(mat), *table))
-
-
-class WideGate(_Prebuilt):
-    """One gate (matrix, dims), k = len(dims) in 1..5, for tensors of one layout.  Validates, plans, packs the table and copies it
-    to `device` once; g(amps) then updates amps IN PLACE with one launch and returns it."""
-
-    def __init__(self, shape, strides, dtype, matrix, dims, device):
-        self._bind(shape, strides, dtype, device)
-        self.k, self._dims, mat = _split_gate(matrix, dims, len(self.shape), "WideGate")
-        self._d = _desc(self.shape, self.strides, dtype)
-        table, info = _wgate_pack(self._d, self.k, self._dims, mat)
-        self.table_bytes, self.tile_bits, self.n_tiles = info.table_bytes, info.tile_bits, info.n_tiles
-        self._upload(table)
-
-    def __call__(self, amps):
-        self._check(amps, "wide_gates.WideGate")
-        with torch.cuda.device(amps.device):
-            _native.check(_native.lib().artn_wgate_apply(ctypes.byref(self._d), amps.data_ptr(), self.k, _ptr(self._dims),
-                                                         self._table.data_ptr(), self.table_bytes,
-                                                         _native.current_stream_ptr(amps.device)))
-        return amps
+    return WideGate._info(shape, strides, matrix, dims, dtype, "wide_gate_info")
 
 
 def apply_wide_gate_(amps, matrix, dims):
@@ -95,39 +116,54 @@ def _width(gate, g):
     return 1 if isinstance(gate[1], (int, np.integer)) else len(gate[1])
 
 
-class FusedCircuit(_Prebuilt):
+class _PartsCircuit(_Prebuilt):
+    """A gate list cut into `parts` that are applied in order; a class declares `_name`, the module-qualified name in messages."""
+
+    _name = None
+
+    def _cut(self, dtype, gates, max_rank, narrow, wider):
+        """The list cut, in order and never reordered, into maximal stretches of gates on one or two dims -- each ONE
+        narrow(..., stretch, device, max_rank) -- and single wider gates, each one wider(width)(..., matrix, dims, device);
+        `wider` may raise.  Sets parts, n_gates, n_launches and table_bytes."""
+        gates = list(gates)
+        if not gates:
+            raise ValueError("at least one gate is needed")
+        self.parts, stretch = [], []
+        for g, gate in enumerate(gates):
+            width = _width(gate, g)
+            if width <= 2:
+                stretch.append(gate)
+                continue
+            if stretch:
+                self.parts.append(narrow(self.shape, self.strides, dtype, stretch, self.device, max_rank))
+                stretch = []
+            self.parts.append(wider(width)(self.shape, self.strides, dtype, gate[0], gate[1], self.device))
+        if stretch:
+            self.parts.append(narrow(self.shape, self.strides, dtype, stretch, self.device, max_rank))
+        self.n_gates = len(gates)
+        self.n_launches = sum(p.n_runs if isinstance(p, narrow) else 1 for p in self.parts)
+        self.table_bytes = sum(p.table_bytes for p in self.parts)
+
+    def __call__(self, amps):
+        self.parts[0]._check(amps, self._name)                 # (no table of its own: a part has its layout, and a table)
+        for part in self.parts:
+            part(amps)
+        return amps
+
+
+class FusedCircuit(_PartsCircuit):
     """An ordered list of gates [(matrix, dims), ...] of ANY width 1..5 for tensors of one layout.  The list is cut, in order,
     into maximal stretches of gates on one or two dims -- each ONE GateCircuit with the given max_rank -- and single gates on
     three to five dims -- each one WideGate; gates are never reordered, and wide gates are not fused into LDS runs.  A circuit
     of narrow gates only is therefore apply_gates_ bit for bit.  circ(amps) updates amps IN PLACE and returns it; n_launches is
     the sum of the stretches' runs plus the number of wide gates."""
 
+    _name = "wide_gates.FusedCircuit"
+
     def __init__(self, shape, strides, dtype, gates, device, max_rank=None):
         self._bind(shape, strides, dtype, device)
-        gates = list(gates)
-        if not gates:
-            raise ValueError("at least one gate is needed")
-        self.parts, stretch = [], []
-        for g, gate in enumerate(gates):
-            if _width(gate, g) <= 2:
-                stretch.append(gate)
-                continue
-            if stretch:
-                self.parts.append(GateCircuit(self.shape, self.strides, dtype, stretch, self.device, max_rank))
-                stretch = []
-            self.parts.append(WideGate(self.shape, self.strides, dtype, gate[0], gate[1], self.device))
-        if stretch:
-            self.parts.append(GateCircuit(self.shape, self.strides, dtype, stretch, self.device, max_rank))
-        self.n_gates = len(gates)
+        self._cut(dtype, gates, max_rank, GateCircuit, lambda width: WideGate)      # (the library refuses a width above five)
         self.n_wide = sum(isinstance(p, WideGate) for p in self.parts)
-        self.n_launches = sum(1 if isinstance(p, WideGate) else p.n_runs for p in self.parts)
-        self.table_bytes = sum(p.table_bytes for p in self.parts)
-
-    def __call__(self, amps):
-        self.parts[0]._check(amps, "wide_gates.FusedCircuit")    # (no table of its own: a part has its layout, and a table)
-        for part in self.parts:
-            part(amps)
-        return amps
 
 
 def apply_circuit_(amps, gates, max_rank=None):
