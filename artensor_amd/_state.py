@@ -141,3 +141,80 @@ class _Prebuilt:
                              f"{tuple(x.shape)}, {tuple(x.stride())}, {x.dtype}")
         if self._table is not None and x.device != self._table.device:
             raise ValueError(f"{what}: built for {self._table.device}, got a tensor on {x.device}")
+
+
+# ---- the run circuits: PauliCircuit, GateCircuit and their two-state forms PauliPairCircuit, GatePairCircuit ---------------------
+def _run_query(entry, info, d, operands, max_rank, outputs, arrays):
+    """One artn_*_query of a run circuit, entry(d, *operands, n, max_rank, info, *outputs): (info,) with nulls for the outputs, or
+    with arrays=True (info, *outputs), a zeroed numpy array per (dtype, width) of `outputs` -- one row per step or gate (the run
+    arrays too: a circuit has no more runs than that), width 0 for a flat one."""
+    n = operands[0].shape[0]
+    out = tuple(np.zeros((n, w) if w else n, dtype=t) for t, w in outputs) if arrays else ()
+    ptrs = [_ptr(x) for x in out] if arrays else [None] * len(outputs)
+    _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), *[_ptr(x) for x in operands], n, max_rank, ctypes.byref(info), *ptrs))
+    return (info,) + out
+
+
+def _run_pack(query, entry, d, operands, max_rank):
+    """(table, info) of a run circuit: query(d, *operands, max_rank) sizes the table that entry(d, *operands, n, max_rank, ...) fills."""
+    return _packed(query(d, *operands, max_rank)[0],
+                   lambda *table: getattr(_native.lib(), entry)(ctypes.byref(d), *[_ptr(x) for x in operands], operands[0].shape[0],
+                                                                max_rank, *table))
+
+
+def _run_keys(info, rank, **run_lists):
+    """What the info dict of every run circuit says of the runs and of the whole circuit; run_lists: key -> its [n, MAX_RANK] array."""
+    nr = info.n_runs
+    ranks = [int(v) for v in rank[:nr]]
+    keys = {"n_measured": info.n_measured} if hasattr(info, "n_measured") else {}
+    keys.update(n_runs=nr, n_launches=info.n_launches, max_rank=info.max_rank, run_rank=ranks)
+    keys.update((key, [[int(v) for v in a[r, :ranks[r]]] for r in range(nr)]) for key, a in run_lists.items())
+    keys.update((key, getattr(info, key)) for key in ("table_bytes", "workspace_bytes", "bytes_read", "bytes_written") if hasattr(info, key))
+    return keys
+
+
+class _RunCircuit(_Prebuilt):
+    """A circuit that the library applies in place as LDS-resident runs, built once for tensors of one layout."""
+
+    def _build(self, shape, strides, dtype, device, max_rank, split, query, pack):
+        """The constructor.  split(n_dims): the operands in the order of the library's entries; query(d, *operands, max_rank) and
+        the name of the pack entry.  Returns (operands, info): the subclass keeps what its calls pass again, under its own names."""
+        self._bind(shape, strides, dtype, device)
+        operands = split(len(self.shape))
+        self._d, self._max_rank = _desc(self.shape, self.strides, dtype), _max_rank(max_rank)
+        table, info = _run_pack(query, pack, self._d, operands, self._max_rank)
+        self._n, self.n_runs, self.max_rank, self.table_bytes = operands[0].shape[0], info.n_runs, info.max_rank, info.table_bytes
+        self._upload(table)
+        return operands, info
+
+    def _run(self, what, entry, amps, *operands):
+        """amps updated in place by entry(d, amps, *operands, n, max_rank, table, ...); returns amps."""
+        self._check(amps, what)
+        with torch.cuda.device(amps.device):
+            _native.check(getattr(_native.lib(), entry)(ctypes.byref(self._d), amps.data_ptr(), *operands, self._n, self._max_rank,
+                                                        self._table.data_ptr(), self.table_bytes,
+                                                        _native.current_stream_ptr(amps.device)))
+        return amps
+
+
+class _PairCircuit(_RunCircuit):
+    """... on two tensors, with the transition element of every measured step or gate; the workspace is allocated per call."""
+
+    def _build(self, *args):
+        operands, info = super()._build(*args)
+        self.workspace_bytes = info.workspace_bytes
+        return operands, info
+
+    def _run(self, what, entry, lam, phi, device, *operands):
+        """Both updated in place by entry(d, lam, phi, *operands, n, max_rank, table, workspace, out, ...); returns t."""
+        for x in (lam, phi):
+            self._check(x, what)
+        if _overlaps(lam, phi):
+            raise ValueError(f"{what}: lam overlaps phi")
+        out = torch.empty((self._n, 2), dtype=torch.float64, device=phi.device)
+        ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)   # (per call: calls may overlap on streams)
+        with torch.cuda.device(phi.device):
+            _native.check(getattr(_native.lib(), entry)(ctypes.byref(self._d), lam.data_ptr(), phi.data_ptr(), *operands, self._n,
+                                                        self._max_rank, self._table.data_ptr(), self.table_bytes, ws.data_ptr(),
+                                                        self.workspace_bytes, out.data_ptr(), _native.current_stream_ptr(phi.device)))
+        return out if device else out.cpu().numpy().view(np.complex128).reshape(self._n)

@@ -12,15 +12,13 @@ After a call both tensors are bit for bit what pauli_evolve_ leaves on each alon
 The transition elements are sums in float64 in a fixed order: bit-identical from run to run for one plan; the order follows the
 blocks of the runs, so they may differ in the last bits between max_rank values.  There is no CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native
-from ._state import _Prebuilt, _checked, _desc, _dtype_code, _max_rank, _overlaps, _packed, _ptr
+from ._state import _PairCircuit, _checked, _desc, _dtype_code, _max_rank, _ptr, _run_keys, _run_query
 from .born import norm2, overlap
-from .pauli import PauliCircuit, PauliSumOperator, _split_steps
+from .pauli import _STEP_ARRAYS, PauliCircuit, PauliSumOperator, _split_steps, _step_keys
 
 __all__ = ["pauli_adjoint_info", "PauliPairCircuit", "pauli_evolve_pair_", "adjoint_gradient"]
 
@@ -36,20 +34,7 @@ def _flags(measure, n_steps):
 
 
 def _adjoint_query(d, ops, coeff, flags, max_rank, arrays=False):
-    n = ops.shape[0]
-    info = _native.ArtnPauliAdjointInfo()
-    if arrays:
-        xm, zm = (np.zeros(n, dtype=np.uint64) for _ in range(2))
-        ny, run, slot, rank = (np.zeros(n, dtype=np.int32) for _ in range(4))
-        basis = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.uint64)
-        pivot = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.int32)
-        out = (xm, zm, ny, run, slot, rank, basis, pivot)
-        ptrs = [_ptr(x) for x in out]
-    else:
-        out, ptrs = (), [None] * 8
-    _native.check(_native.lib().artn_pauli_adjoint_query(ctypes.byref(d), _ptr(ops), _ptr(coeff), _ptr(flags), n, max_rank,
-                                                         ctypes.byref(info), *ptrs))
-    return (info,) + out
+    return _run_query("artn_pauli_adjoint_query", _native.ArtnPauliAdjointInfo(), d, (ops, coeff, flags), max_rank, _STEP_ARRAYS, arrays)
 
 
 def pauli_adjoint_info(shape, strides, steps, dtype=torch.complex64, measure=None, max_rank=None):
@@ -60,21 +45,11 @@ def pauli_adjoint_info(shape, strides, steps, dtype=torch.complex64, measure=Non
     _dtype_code(dtype, "pauli_adjoint_info")
     coeff, ops = _split_steps(steps, len(shape))
     flags = _flags(measure, ops.shape[0])
-    info, xm, zm, ny, run, slot, rank, basis, pivot = _adjoint_query(_desc(shape, strides, dtype), ops, coeff, flags,
-                                                                     _max_rank(max_rank), arrays=True)
-    nr = info.n_runs
-    ranks = [int(v) for v in rank[:nr]]
-    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny],
-            "alpha": [complex(c[0], c[1]) for c in coeff], "beta": [complex(c[2], c[3]) for c in coeff],
-            "run": [int(v) for v in run], "slot_mask": [int(v) for v in slot], "measure": [bool(f) for f in flags],
-            "n_measured": info.n_measured, "n_runs": nr, "n_launches": info.n_launches, "max_rank": info.max_rank, "run_rank": ranks,
-            "run_basis": [[int(v) for v in basis[r, :ranks[r]]] for r in range(nr)],
-            "run_pivot": [[int(v) for v in pivot[r, :ranks[r]]] for r in range(nr)],
-            "table_bytes": info.table_bytes, "workspace_bytes": info.workspace_bytes, "bytes_read": info.bytes_read,
-            "bytes_written": info.bytes_written}
+    info, *per_step, rank, basis, pivot = _adjoint_query(_desc(shape, strides, dtype), ops, coeff, flags, _max_rank(max_rank), arrays=True)
+    return {**_step_keys(coeff, *per_step), "measure": [bool(f) for f in flags], **_run_keys(info, rank, run_basis=basis, run_pivot=pivot)}
 
 
-class PauliPairCircuit(_Prebuilt):
+class PauliPairCircuit(_PairCircuit):
     """The steps of a PauliCircuit for TWO tensors of one layout: validates, cuts the runs, packs the table and copies it to
     `device` once; the workspace is allocated per call, so an instance holds no state that two calls share.  circ(lam, phi,
     device=False) updates both IN PLACE (one launch per run and a finish launch) and returns t[k] = <lam| P_k |phi> taken
@@ -82,33 +57,15 @@ class PauliPairCircuit(_Prebuilt):
     tensor [K, 2] without a host synchronisation."""
 
     def __init__(self, shape, strides, dtype, steps, device, measure=None, max_rank=None):
-        self._bind(shape, strides, dtype, device)
-        coeff, self._ops = _split_steps(steps, len(self.shape))
-        flags = _flags(measure, self._ops.shape[0])
-        self._d = _desc(self.shape, self.strides, dtype)
-        self._max_rank = _max_rank(max_rank)
-        table, info = _packed(_adjoint_query(self._d, self._ops, coeff, flags, self._max_rank)[0],
-                              lambda *table: _native.lib().artn_pauli_adjoint_pack(ctypes.byref(self._d), _ptr(self._ops), _ptr(coeff),
-                                                                                   _ptr(flags), self._ops.shape[0], self._max_rank,
-                                                                                   *table))
-        self.n_steps, self.n_runs, self.max_rank = self._ops.shape[0], info.n_runs, info.max_rank
-        self.table_bytes, self.workspace_bytes = info.table_bytes, info.workspace_bytes
-        self._upload(table)
+        def split(n_dims):
+            coeff, ops = _split_steps(steps, n_dims)
+            return ops, coeff, _flags(measure, ops.shape[0])
+
+        (self._ops, _, _), _ = self._build(shape, strides, dtype, device, max_rank, split, _adjoint_query, "artn_pauli_adjoint_pack")
+        self.n_steps = self._n
 
     def __call__(self, lam, phi, device=False):
-        what = "adjoint.PauliPairCircuit"
-        for x in (lam, phi):
-            self._check(x, what)
-        if _overlaps(lam, phi):
-            raise ValueError(f"{what}: lam overlaps phi")
-        out = torch.empty((self.n_steps, 2), dtype=torch.float64, device=phi.device)
-        ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)   # (per call: calls may overlap on streams)
-        with torch.cuda.device(phi.device):
-            _native.check(_native.lib().artn_pauli_adjoint(ctypes.byref(self._d), lam.data_ptr(), phi.data_ptr(), _ptr(self._ops),
-                                                           self.n_steps, self._max_rank, self._table.data_ptr(), self.table_bytes,
-                                                           ws.data_ptr(), self.workspace_bytes, out.data_ptr(),
-                                                           _native.current_stream_ptr(phi.device)))
-        return out if device else out.cpu().numpy().view(np.complex128).reshape(self.n_steps)
+        return self._run("adjoint.PauliPairCircuit", "artn_pauli_adjoint", lam, phi, device, _ptr(self._ops))
 
 
 def pauli_evolve_pair_(lam, phi, steps, measure=None, max_rank=None, device=False):
@@ -116,6 +73,27 @@ def pauli_evolve_pair_(lam, phi, steps, measure=None, max_rank=None, device=Fals
     measured steps (see PauliPairCircuit)."""
     _checked(phi, "adjoint.pauli_evolve_pair_")
     return PauliPairCircuit(phi.shape, phi.stride(), phi.dtype, steps, phi.device, measure, max_rank)(lam, phi, device)
+
+
+def _adjoint_sweep(amps0, forward, sweep, terms, index, derivative, normalize):
+    """(E, grad), the second half of both adjoint gradients: a copy of amps0 through the circuit forward() builds, H|phi>, the energy,
+    the sweep of the reversed circuit, and grad[index[k]] += derivative(t) of position k's transition element in float64, in
+    circuit order (index -1: not a parameter)."""
+    shape, strides, dtype, dev = amps0.shape, amps0.stride(), amps0.dtype, amps0.device
+    phi = torch.empty_strided(shape, strides, dtype=dtype, device=dev)
+    phi.copy_(amps0)
+    forward()(phi)
+    lam = PauliSumOperator(shape, strides, dtype, terms, dev)(phi)
+    energy = overlap(phi, lam)[0].real
+    t = sweep(lam, phi)
+    grad = np.zeros(max(index, default=-1) + 1, dtype=np.float64)
+    for k, p in enumerate(index):
+        if p >= 0:
+            grad[p] += derivative(t[len(index) - 1 - k])
+    if normalize:
+        n2 = norm2(amps0)
+        energy, grad = energy / n2, grad / n2
+    return energy, grad
 
 
 def adjoint_gradient(amps0, rotations, terms, params=None, normalize=True, max_rank=None):
@@ -139,22 +117,10 @@ def adjoint_gradient(amps0, rotations, terms, params=None, normalize=True, max_r
         params = [int(p) for p in params]
         if len(params) != n_rot or any(p < -1 for p in params):
             raise ValueError(f"params: one integer >= -1 per rotation expected ({n_rot})")
-    shape, strides, dtype, dev = amps0.shape, amps0.stride(), amps0.dtype, amps0.device
+    layout = (amps0.shape, amps0.stride(), amps0.dtype)
     back = [(-float(theta), string) for theta, string in reversed(rotations)]
     # built first: max_rank follows the two-state limits, and a refusal comes before any work on the device
-    sweep = PauliPairCircuit(shape, strides, dtype, back, dev, [p >= 0 for p in reversed(params)], max_rank)
-    phi = torch.empty_strided(shape, strides, dtype=dtype, device=dev)
-    phi.copy_(amps0)
-    PauliCircuit(shape, strides, dtype, rotations, dev, max_rank)(phi)
-    lam = PauliSumOperator(shape, strides, dtype, terms, dev)(phi)
-    energy = overlap(phi, lam)[0].real
-    t = sweep(lam, phi)
+    sweep = PauliPairCircuit(*layout, back, amps0.device, [p >= 0 for p in reversed(params)], max_rank)
     # the sweep runs with the negated angles: U_k^+ = exp(+i theta_k P_k), and t is taken before U_k^+ is applied
-    grad = np.zeros(max(params) + 1 if params else 0, dtype=np.float64)
-    for k, p in enumerate(params):
-        if p >= 0:
-            grad[p] += 2.0 * t[n_rot - 1 - k].imag
-    if normalize:
-        n2 = norm2(amps0)
-        energy, grad = energy / n2, grad / n2
-    return energy, grad
+    return _adjoint_sweep(amps0, lambda: PauliCircuit(*layout, rotations, amps0.device, max_rank), sweep, terms, params,
+                          lambda t: 2.0 * t.imag, normalize)

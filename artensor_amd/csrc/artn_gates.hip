@@ -1,5 +1,6 @@
 // artn_gates.hip -- host half of the dense-gate entry points of include/artn.h (kernels: artn_gates_kernel.h; the same circuits on
-// two states with transition elements: artn_gates_adjoint_kernel.h).
+// two states with transition elements: artn_gates_adjoint_kernel.h).  What the circuits share with the Pauli circuits of
+// artn_pauli.hip -- run records, launchers, apply entries -- is artn_run_circuit_host.h.
 //
 // A translation unit of its own (build/obj/gates.o).
 #include <hip/hip_runtime.h>
@@ -12,13 +13,14 @@
 #include "artn_state_host.h"
 #include "artn_gates_kernel.h"
 #include "artn_gates_adjoint_kernel.h"
+#include "artn_run_circuit_host.h"
 
 struct GatesRunPlan {
   int64_t first = 0, count = 0;
   std::vector<int> pivot; // the distinct high target bits, ascending once the run is closed
 };
 struct GatesPlan {
-  int64_t n = 1;
+  int64_t n = 1, n_recs = 0;               // elements; gates
   std::vector<int32_t> k, bits;            // bits: [n_gates][2] in the order the dims are listed, -1 for the absent one
   std::vector<int32_t> run_of, slot_mask, flags;
   std::vector<GatesRunPlan> runs;
@@ -37,6 +39,7 @@ static int gates_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t
   if (int rc = state_layout(d, l)) return rc;
   if (int rc = state_bits_only(l, "gate circuits take")) return rc;
   const int64_t n = gp.n = l.n;
+  gp.n_recs = n_gates;
   if (int rc = state_max_rank(d->dtype, max_rank, ARTN_GATES_MAX_RANK, false, max_rank)) return rc;
   if (n_gates > INT32_MAX) return fail(ARTN_E_UNSUPPORTED, "too many gates in one circuit");
   gp.k.assign(k, k + n_gates), gp.bits.assign(2 * n_gates, -1), gp.flags.assign(n_gates, 0);
@@ -103,17 +106,21 @@ static int gates_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t
   return ARTN_OK;
 }
 
-// the header and the run records of a table (include/artn.h: TABLE)
-static void gates_fill_runs(const GatesPlan &gp, ArtnGatesHeader *h, ArtnGatesRun *runs) {
-  *h = ArtnGatesHeader{(uint64_t)gp.runs.size(), (uint64_t)gp.k.size(), (uint64_t)gp.info.max_rank, 0};
-  for (size_t r = 0; r < gp.runs.size(); ++r) {
-    const GatesRunPlan &rp = gp.runs[r];
-    ArtnGatesRun rec = {};
-    rec.first = (uint64_t)rp.first, rec.count = (uint64_t)rp.count, rec.rank = (uint64_t)rp.pivot.size();
-    for (size_t j = 0; j < rp.pivot.size(); ++j) rec.pivot[j] = (uint64_t)rp.pivot[j];
-    runs[r] = rec;
-  }
-}
+// what the shared host half (artn_run_circuit_host.h) reads of the family
+struct GatesFamily {
+  using Plan = GatesPlan;
+  using Header = ArtnGatesHeader;
+  using Run = ArtnGatesRun;
+  using Rec = ArtnGatesGate;
+  static constexpr int MAX_RANK = ARTN_GATES_MAX_RANK;
+  static constexpr long MAX_GRID = ARTN_GATES_MAX_GRID;
+  static constexpr const char *query = "artn_gates_query", *apply = "artn_gates_apply";
+  static void basis(const GatesRunPlan &, Run &) {}
+  template <typename T, int R>
+  static constexpr auto run = artn_k_gates<T, R>;
+  template <typename T>
+  static constexpr auto small = artn_k_gates_small<T>;
+};
 
 // the record of gate g
 static ArtnGatesGate gates_fill_gate(const GatesPlan &gp, int64_t g, const double *mat) {
@@ -136,47 +143,9 @@ static ArtnGatesGate gates_fill_gate(const GatesPlan &gp, int64_t g, const doubl
 // the per-gate and per-run arrays of a query (any may be null)
 static void gates_report(const GatesPlan &gp, int32_t *bits, int32_t *run, int32_t *slot_mask, int32_t *local, int32_t *run_rank,
                          int32_t *run_pivot) {
-  const int64_t n_gates = (int64_t)gp.k.size();
   if (bits) std::copy(gp.bits.begin(), gp.bits.end(), bits);
-  if (run) std::copy(gp.run_of.begin(), gp.run_of.end(), run);
-  if (slot_mask) std::copy(gp.slot_mask.begin(), gp.slot_mask.end(), slot_mask);
-  if (local)
-    for (int64_t g = 0; g < n_gates; ++g) local[g] = (gp.flags[g] & ARTN_GATE_LOCAL) ? 1 : 0;
-  for (size_t r = 0; r < gp.runs.size(); ++r) {
-    const GatesRunPlan &rp = gp.runs[r];
-    if (run_rank) run_rank[r] = (int32_t)rp.pivot.size();
-    if (run_pivot)
-      for (size_t j = 0; j < ARTN_GATES_MAX_RANK; ++j) run_pivot[r * ARTN_GATES_MAX_RANK + j] = j < rp.pivot.size() ? rp.pivot[j] : -1;
-  }
-}
-
-template <typename T, int R>
-static hipError_t gates_launch_rank(T *a, long tiles, const ArtnGatesRun *run, const ArtnGatesGate *gates, hipStream_t st) {
-  const size_t lds = ((size_t)sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
-  if (hipError_t e = ensure_lds<artn_k_gates<T, R>>(lds); e != hipSuccess) return e;
-  const long n_blocks = tiles >> R;
-  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_GATES_MAX_GRID));
-  hipLaunchKernelGGL((artn_k_gates<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, a, n_blocks, run, gates);
-  return hipSuccess;
-}
-
-template <typename T>
-static hipError_t gates_launch(const GatesPlan &gp, T *a, const void *table, hipStream_t st) {
-  const ArtnGatesRun *runs;
-  const ArtnGatesGate *gates;
-  state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
-  if (gp.n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
-    hipLaunchKernelGGL(artn_k_gates_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, a, (long)gp.n, gates, (int)gp.k.size());
-    return hipSuccess;
-  }
-  const long tiles = (long)(gp.n >> ARTN_PAULI_TILE_BITS);
-  for (size_t r = 0; r < gp.runs.size(); ++r) {
-    const hipError_t e = state_with_rank<T, ARTN_GATES_MAX_RANK>((int)gp.runs[r].pivot.size(), [&](auto rank) {
-      return gates_launch_rank<T, decltype(rank)::value>(a, tiles, runs + r, gates, st);
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  for (int64_t g = 0; local && g < gp.n_recs; ++g) local[g] = (gp.flags[g] & ARTN_GATE_LOCAL) ? 1 : 0;
+  run_circuit_report<GatesFamily>(gp, run, slot_mask, run_rank, run_pivot);
 }
 
 extern "C" {
@@ -204,25 +173,15 @@ int artn_gates_pack(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *
   ArtnGatesRun *runs;
   ArtnGatesGate *gates;
   state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
-  gates_fill_runs(gp, (ArtnGatesHeader *)table, runs);
+  run_circuit_fill_runs<GatesFamily>(gp, table, runs);
   for (int64_t g = 0; g < n_gates; ++g) gates[g] = gates_fill_gate(gp, g, mat);
   return ARTN_OK;
 }
 
 int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const int32_t *dims, const double *mat, int64_t n_gates,
                      int32_t max_rank, const void *table, int64_t table_bytes, void *stream) {
-  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
-  GatesPlan gp;
-  if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, gp)) return rc;
-  if (!a || !table) return fail(ARTN_E_INVALID, "null pointer");
-  if (int rc = state_table_fits(table_bytes, gp.info.table_bytes, "artn_gates_query")) return rc;
-  if (int rc = state_array_aligned(a, "artn_gates_apply")) return rc;
-  if (int rc = state_table_aligned(table, "artn_gates_apply")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == ARTN_C64) HIP_TRY(gates_launch(gp, (float2 *)a, table, st));
-  else HIP_TRY(gates_launch(gp, (double2 *)a, table, st));
-  HIP_TRY(hipGetLastError());
-  return ARTN_OK;
+  return run_circuit_apply<GatesFamily>(d, a, table, table_bytes, stream,
+                                        [&](GatesPlan &gp) { return gates_plan(d, k, dims, mat, n_gates, max_rank, gp); });
 }
 
 } // extern "C"
@@ -230,18 +189,30 @@ int artn_gates_apply(const ArtnMarginalDesc *d, void *a, const int32_t *k, const
 // The same circuits on two states with transition elements (include/artn.h: GATE ADJOINT; kernels: artn_gates_adjoint_kernel.h).
 // The plan is gates_plan at the two-state rank; only the limits, the measure, the byte counts and the workspace are the adjoint's own.
 struct GatesAdjointPlan {
-  GatesPlan gp;
+  GatesPlan one;
   std::vector<uint8_t> flag, diag; // per gate: measured; its M is diagonal
   ArtnGatesAdjointInfo info = {};
+};
+struct GatesAdjointFamily {
+  using One = GatesFamily;
+  using Plan = GatesAdjointPlan;
+  using Info = ArtnGatesAdjointInfo;
+  using Rec = ArtnGatesAdjointGate;
+  static constexpr int MAX_RANK = ARTN_GATES_ADJOINT_MAX_RANK;
+  static constexpr const char *query = "artn_gates_adjoint_query", *apply = "artn_gates_adjoint";
+  template <typename T, int R>
+  static constexpr auto run = artn_k_gates_adjoint<T, R>;
+  template <typename T>
+  static constexpr auto small = artn_k_gates_adjoint_small<T>;
+  static constexpr auto finish = artn_k_gates_adjoint_finish;
 };
 
 // `mat` and the measure may be null (artn_gates_adjoint: they are in the table).
 static int gates_adjoint_plan(const ArtnMarginalDesc *d, const int32_t *k, const int32_t *dims, const double *mat, const double *measure_mat,
                               const uint8_t *measure_flag, int64_t n_gates, int32_t max_rank, GatesAdjointPlan &ap) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (int rc = state_max_rank(d->dtype, max_rank, ARTN_GATES_ADJOINT_MAX_RANK, true, max_rank)) return rc;
-  if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, ap.gp)) return rc;
-  const GatesPlan &gp = ap.gp;
+  if (int rc = run_pair_rank<GatesAdjointFamily>(d, max_rank)) return rc;
+  if (int rc = gates_plan(d, k, dims, mat, n_gates, max_rank, ap.one)) return rc;
+  const GatesPlan &gp = ap.one;
   ap.flag.assign(n_gates, 0), ap.diag.assign(n_gates, 0);
   int64_t flagged = 0;
   for (int64_t g = 0; measure_flag && g < n_gates; ++g) {
@@ -252,52 +223,10 @@ static int gates_adjoint_plan(const ArtnMarginalDesc *d, const int32_t *k, const
       return fail(ARTN_E_INVALID, "gate " + std::to_string(g) + ": an entry of the measure matrix is not finite");
     ap.flag[g] = 1, ap.diag[g] = diagonal, ++flagged;
   }
-  const int64_t groups = std::min<int64_t>(std::max<int64_t>(gp.n >> ARTN_PAULI_TILE_BITS, 1), ARTN_GATES_MAX_GRID);
-  ap.info = ArtnGatesAdjointInfo{};
-  ap.info.n_runs = gp.info.n_runs;
-  ap.info.n_launches = gp.info.n_runs + 1;
-  ap.info.max_rank = gp.info.max_rank;
-  ap.info.n_measured = (int32_t)flagged;
+  run_pair_info<GatesAdjointFamily>(ap, flagged);
   ap.info.table_bytes = (int64_t)sizeof(ArtnGatesHeader) + (int64_t)gp.runs.size() * (int64_t)sizeof(ArtnGatesRun) +
                         n_gates * (int64_t)sizeof(ArtnGatesAdjointGate);
-  ap.info.workspace_bytes = n_gates * groups * ARTN_PAULI_ADJOINT_WAVES * 2 * (int64_t)sizeof(double);
-  ap.info.bytes_read = 2 * gp.info.bytes_read;
-  ap.info.bytes_written = 2 * gp.info.bytes_written;
   return ARTN_OK;
-}
-
-template <typename T, int R>
-static hipError_t gates_adjoint_launch_rank(T *lam, T *phi, long tiles, const ArtnGatesRun *run, const ArtnGatesAdjointGate *gates, double *ws,
-                                            long groups, hipStream_t st) {
-  const size_t lds = ((size_t)2 * sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
-  if (hipError_t e = ensure_lds<artn_k_gates_adjoint<T, R>>(lds); e != hipSuccess) return e;
-  const long n_blocks = tiles >> R;
-  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_GATES_MAX_GRID)); // (at most `groups`: the workspace slots of a gate)
-  hipLaunchKernelGGL((artn_k_gates_adjoint<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, lam, phi, n_blocks, run, gates, ws, groups);
-  return hipSuccess;
-}
-
-template <typename T>
-static hipError_t gates_adjoint_launch(const GatesPlan &gp, T *lam, T *phi, const void *table, double *ws, double *out, hipStream_t st) {
-  const ArtnGatesRun *runs;
-  const ArtnGatesAdjointGate *gates;
-  state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
-  const int n_gates = (int)gp.k.size();
-  const long tiles = (long)std::max<int64_t>(gp.n >> ARTN_PAULI_TILE_BITS, 1);
-  const long groups = std::min<long>(tiles, ARTN_GATES_MAX_GRID);
-  if (gp.n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
-    hipLaunchKernelGGL(artn_k_gates_adjoint_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, lam, phi, (long)gp.n, gates, n_gates, ws);
-  } else {
-    for (size_t r = 0; r < gp.runs.size(); ++r) {
-      const hipError_t e = state_with_rank<T, ARTN_GATES_ADJOINT_MAX_RANK>((int)gp.runs[r].pivot.size(), [&](auto rank) {
-        return gates_adjoint_launch_rank<T, decltype(rank)::value>(lam, phi, tiles, runs + r, gates, ws, groups, st);
-      });
-      if (e != hipSuccess) return e;
-    }
-  }
-  hipLaunchKernelGGL(artn_k_gates_adjoint_finish, dim3((unsigned)n_gates), dim3(ARTN_BORN_THREADS), 0, st, (const double *)ws, groups, tiles,
-                     gates, out);
-  return hipSuccess;
 }
 
 extern "C" {
@@ -311,7 +240,7 @@ int artn_gates_adjoint_query(const ArtnMarginalDesc *d, const int32_t *k, const 
   GatesAdjointPlan ap;
   if (int rc = gates_adjoint_plan(d, k, dims, mat, measure_mat, measure_flag, n_gates, max_rank, ap)) return rc;
   *info = ap.info;
-  gates_report(ap.gp, bits, run, slot_mask, local, run_rank, run_pivot);
+  gates_report(ap.one, bits, run, slot_mask, local, run_rank, run_pivot);
   return ARTN_OK;
 }
 
@@ -324,11 +253,11 @@ int artn_gates_adjoint_pack(const ArtnMarginalDesc *d, const int32_t *k, const i
   if (!table) return fail(ARTN_E_INVALID, "null pointer");
   if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_gates_adjoint_query")) return rc;
   if (int rc = state_table_aligned(table, "artn_gates_adjoint_pack")) return rc;
-  const GatesPlan &gp = ap.gp;
+  const GatesPlan &gp = ap.one;
   ArtnGatesRun *runs;
   ArtnGatesAdjointGate *gates;
   state_table_parts<ArtnGatesHeader>(table, gp.runs.size(), runs, gates);
-  gates_fill_runs(gp, (ArtnGatesHeader *)table, runs);
+  run_circuit_fill_runs<GatesFamily>(gp, table, runs);
   for (int64_t g = 0; g < n_gates; ++g) {
     ArtnGatesAdjointGate rec = {};
     rec.g = gates_fill_gate(gp, g, mat);
@@ -346,21 +275,9 @@ int artn_gates_adjoint_pack(const ArtnMarginalDesc *d, const int32_t *k, const i
 int artn_gates_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const int32_t *k, const int32_t *dims, int64_t n_gates,
                        int32_t max_rank, const void *table, int64_t table_bytes, void *workspace, int64_t workspace_bytes,
                        double *out, void *stream) {
-  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
-  GatesAdjointPlan ap;
-  if (int rc = gates_adjoint_plan(d, k, dims, nullptr, nullptr, nullptr, n_gates, max_rank, ap)) return rc; // (matrices and flags are in the table)
-  if (!lam || !phi || !table || !workspace || !out) return fail(ARTN_E_INVALID, "null pointer");
-  if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_gates_adjoint_query")) return rc;
-  if (workspace_bytes < ap.info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_gates_adjoint_query reports");
-  if ((((uintptr_t)lam | (uintptr_t)phi | (uintptr_t)workspace) & 15) != 0)
-    return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint needs 16-byte aligned arrays and workspace");
-  if ((((uintptr_t)table | (uintptr_t)out) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_gates_adjoint needs an 8-byte aligned table and output");
-  if (int rc = state_disjoint(lam, phi, (uintptr_t)ap.gp.n * (d->dtype == ARTN_C64 ? 8 : 16), "artn_gates_adjoint")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == ARTN_C64) HIP_TRY(gates_adjoint_launch(ap.gp, (float2 *)lam, (float2 *)phi, table, (double *)workspace, out, st));
-  else HIP_TRY(gates_adjoint_launch(ap.gp, (double2 *)lam, (double2 *)phi, table, (double *)workspace, out, st));
-  HIP_TRY(hipGetLastError());
-  return ARTN_OK;
+  return run_pair_apply<GatesAdjointFamily>(d, lam, phi, table, table_bytes, workspace, workspace_bytes, out, stream, [&](GatesAdjointPlan &ap) {
+    return gates_adjoint_plan(d, k, dims, nullptr, nullptr, nullptr, n_gates, max_rank, ap); // (matrices and flags are in the table)
+  });
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // artn_pauli.hip -- host half of the Pauli-string entry points of include/artn.h (kernels: artn_pauli_kernel.h for the
 // expectation values, artn_pauli_apply_kernel.h for y = H a, artn_pauli_evolve_kernel.h for the in-place circuits,
-// artn_pauli_adjoint_kernel.h for the same circuits on two states with transition elements).
+// artn_pauli_adjoint_kernel.h for the same circuits on two states with transition elements).  What the circuits share with
+// the gate circuits of artn_gates.hip -- run records, launchers, apply entries -- is artn_run_circuit_host.h.
 //
 // A translation unit of its own (build/obj/pauli.o).
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include "artn_pauli_apply_kernel.h"
 #include "artn_pauli_evolve_kernel.h"
 #include "artn_pauli_adjoint_kernel.h"
+#include "artn_run_circuit_host.h"
 
 struct PauliPlan {
   int64_t n = 1;
@@ -272,6 +274,7 @@ struct PauliEvolveRunPlan {
 };
 struct PauliEvolvePlan {
   PauliPlan pl;
+  int64_t n = 1, n_recs = 0; // pl.n and the steps
   std::vector<PauliEvolveRunPlan> runs;
   std::vector<int32_t> run_of, slot_mask;
   ArtnPauliEvolveInfo info = {};
@@ -295,6 +298,7 @@ static int pauli_evolve_plan(const ArtnMarginalDesc *d, const uint8_t *ops, int6
   if (n_steps > INT32_MAX) return fail(ARTN_E_UNSUPPORTED, "too many steps in one circuit");
   const int cap = state_rank_cap(pl.n, ARTN_PAULI_TILE_BITS, max_rank);
   const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
+  ep.n = pl.n, ep.n_recs = n_steps;
   ep.run_of.assign(n_steps, 0), ep.slot_mask.assign(n_steps, 0);
   PauliEvolveRunPlan cur;
   auto close = [&]() {
@@ -337,35 +341,22 @@ static int pauli_evolve_plan(const ArtnMarginalDesc *d, const uint8_t *ops, int6
   return ARTN_OK;
 }
 
-template <typename T, int R>
-static hipError_t pauli_evolve_launch_rank(T *a, long tiles, const ArtnPauliEvolveRun *run, const ArtnPauliEvolveStep *stp, hipStream_t st) {
-  const size_t lds = ((size_t)sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
-  if (hipError_t e = ensure_lds<artn_k_pauli_evolve<T, R>>(lds); e != hipSuccess) return e;
-  const long n_blocks = tiles >> R;
-  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_PAULI_EVOLVE_MAX_GRID));
-  hipLaunchKernelGGL((artn_k_pauli_evolve<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, a, n_blocks, run, stp);
-  return hipSuccess;
-}
 
-template <typename T>
-static hipError_t pauli_evolve_launch(const PauliEvolvePlan &ep, T *a, const void *table, hipStream_t st) {
-  const ArtnPauliEvolveRun *runs;
-  const ArtnPauliEvolveStep *stp;
-  state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
-  const int64_t n = ep.pl.n;
-  if (n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
-    hipLaunchKernelGGL(artn_k_pauli_evolve_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, a, (long)n, stp, (int)ep.pl.xm.size());
-    return hipSuccess;
-  }
-  const long tiles = (long)(n >> ARTN_PAULI_TILE_BITS);
-  for (size_t r = 0; r < ep.runs.size(); ++r) {
-    const hipError_t e = state_with_rank<T, ARTN_PAULI_EVOLVE_MAX_RANK>((int)ep.runs[r].basis.size(), [&](auto rank) {
-      return pauli_evolve_launch_rank<T, decltype(rank)::value>(a, tiles, runs + r, stp, st);
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+// what the shared host half (artn_run_circuit_host.h) reads of the family
+struct PauliEvolveFamily {
+  using Plan = PauliEvolvePlan;
+  using Header = ArtnPauliEvolveHeader;
+  using Run = ArtnPauliEvolveRun;
+  using Rec = ArtnPauliEvolveStep;
+  static constexpr int MAX_RANK = ARTN_PAULI_EVOLVE_MAX_RANK;
+  static constexpr long MAX_GRID = ARTN_PAULI_EVOLVE_MAX_GRID;
+  static constexpr const char *query = "artn_pauli_evolve_query", *apply = "artn_pauli_evolve";
+  static void basis(const PauliEvolveRunPlan &rp, Run &rec) { std::copy(rp.basis.begin(), rp.basis.end(), rec.basis); }
+  template <typename T, int R>
+  static constexpr auto run = artn_k_pauli_evolve<T, R>;
+  template <typename T>
+  static constexpr auto small = artn_k_pauli_evolve_small<T>;
+};
 
 // the per-step and per-run arrays of a query (any may be NULL)
 static void pauli_evolve_report(const PauliEvolvePlan &ep, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *run, int32_t *slot_mask,
@@ -374,35 +365,21 @@ static void pauli_evolve_report(const PauliEvolvePlan &ep, uint64_t *xmask, uint
   if (xmask) std::copy(pl.xm.begin(), pl.xm.end(), xmask);
   if (zmask) std::copy(pl.zm.begin(), pl.zm.end(), zmask);
   if (n_y) std::copy(pl.ny.begin(), pl.ny.end(), n_y);
-  if (run) std::copy(ep.run_of.begin(), ep.run_of.end(), run);
-  if (slot_mask) std::copy(ep.slot_mask.begin(), ep.slot_mask.end(), slot_mask);
-  for (size_t r = 0; r < ep.runs.size(); ++r) {
-    const PauliEvolveRunPlan &rp = ep.runs[r];
-    if (run_rank) run_rank[r] = (int32_t)rp.basis.size();
-    for (size_t j = 0; j < ARTN_PAULI_EVOLVE_MAX_RANK; ++j) {
-      if (run_basis) run_basis[r * ARTN_PAULI_EVOLVE_MAX_RANK + j] = j < rp.basis.size() ? rp.basis[j] : 0;
-      if (run_pivot) run_pivot[r * ARTN_PAULI_EVOLVE_MAX_RANK + j] = j < rp.pivot.size() ? rp.pivot[j] : -1;
-    }
-  }
+  run_circuit_report<PauliEvolveFamily>(ep, run, slot_mask, run_rank, run_pivot);
+  for (size_t r = 0; run_basis && r < ep.runs.size(); ++r)
+    for (size_t j = 0; j < ARTN_PAULI_EVOLVE_MAX_RANK; ++j)
+      run_basis[r * ARTN_PAULI_EVOLVE_MAX_RANK + j] = j < ep.runs[r].basis.size() ? ep.runs[r].basis[j] : 0;
 }
 
 // the table of include/artn.h into host memory (at least ep.info.table_bytes)
 static void pauli_evolve_fill(const PauliEvolvePlan &ep, const double *coeff, void *table) {
   const PauliPlan &pl = ep.pl;
-  const int64_t n_steps = (int64_t)pl.xm.size();
   const uint64_t in = ((uint64_t)1 << ARTN_PAULI_TILE_BITS) - 1;
   ArtnPauliEvolveRun *runs;
   ArtnPauliEvolveStep *stp;
   state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
-  *(ArtnPauliEvolveHeader *)table = ArtnPauliEvolveHeader{(uint64_t)ep.runs.size(), (uint64_t)n_steps, (uint64_t)ep.info.max_rank, 0};
-  for (size_t r = 0; r < ep.runs.size(); ++r) {
-    const PauliEvolveRunPlan &rp = ep.runs[r];
-    ArtnPauliEvolveRun rec = {};
-    rec.first = (uint64_t)rp.first, rec.count = (uint64_t)rp.count, rec.rank = (uint64_t)rp.basis.size();
-    for (size_t j = 0; j < rp.basis.size(); ++j) rec.basis[j] = rp.basis[j], rec.pivot[j] = (uint64_t)rp.pivot[j];
-    runs[r] = rec;
-  }
-  for (int64_t k = 0; k < n_steps; ++k) {
+  run_circuit_fill_runs<PauliEvolveFamily>(ep, table, runs);
+  for (int64_t k = 0; k < ep.n_recs; ++k) {
     // (below one tile the small kernel reads the whole xmask here: it has no bits above the tile)
     stp[k] = ArtnPauliEvolveStep{pl.xm[k] & in, (uint64_t)ep.slot_mask[k], pl.zm[k], (uint64_t)pl.ny[k],
                                  coeff[4 * k], coeff[4 * k + 1], coeff[4 * k + 2], coeff[4 * k + 3]};
@@ -436,77 +413,40 @@ int artn_pauli_evolve_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const 
 
 int artn_pauli_evolve(const ArtnMarginalDesc *d, void *a, const uint8_t *ops, int64_t n_steps, int32_t max_rank, const void *table,
                       int64_t table_bytes, void *stream) {
-  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
-  PauliEvolvePlan ep;
-  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc; // (the coefficients are in the table)
-  if (!a || !table) return fail(ARTN_E_INVALID, "null pointer");
-  if (int rc = state_table_fits(table_bytes, ep.info.table_bytes, "artn_pauli_evolve_query")) return rc;
-  if (int rc = state_array_aligned(a, "artn_pauli_evolve")) return rc;
-  if (int rc = state_table_aligned(table, "artn_pauli_evolve")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == ARTN_C64) HIP_TRY(pauli_evolve_launch(ep, (float2 *)a, table, st));
-  else HIP_TRY(pauli_evolve_launch(ep, (double2 *)a, table, st));
-  HIP_TRY(hipGetLastError());
-  return ARTN_OK;
+  return run_circuit_apply<PauliEvolveFamily>(d, a, table, table_bytes, stream, [&](PauliEvolvePlan &ep) {
+    return pauli_evolve_plan(d, ops, n_steps, max_rank, ep); // (the coefficients are in the table)
+  });
 }
 
 } // extern "C"
 
 // The same circuits on two states with transition elements (include/artn.h: ADJOINT; kernels: artn_pauli_adjoint_kernel.h).
 // The plan is pauli_evolve_plan at the two-state rank; only the limits, the byte counts and the workspace are the adjoint's own.
+struct PauliAdjointPlan {
+  PauliEvolvePlan one;
+  ArtnPauliAdjointInfo info = {};
+};
+struct PauliAdjointFamily {
+  using One = PauliEvolveFamily;
+  using Plan = PauliAdjointPlan;
+  using Info = ArtnPauliAdjointInfo;
+  using Rec = ArtnPauliEvolveStep;
+  static constexpr int MAX_RANK = ARTN_PAULI_ADJOINT_MAX_RANK;
+  static constexpr const char *query = "artn_pauli_adjoint_query", *apply = "artn_pauli_adjoint";
+  template <typename T, int R>
+  static constexpr auto run = artn_k_pauli_adjoint<T, R>;
+  template <typename T>
+  static constexpr auto small = artn_k_pauli_adjoint_small<T>;
+  static constexpr auto finish = artn_k_pauli_adjoint_finish;
+};
+
 static int pauli_adjoint_plan(const ArtnMarginalDesc *d, const uint8_t *ops, const uint8_t *measure, int64_t n_steps, int32_t max_rank,
-                              PauliEvolvePlan &ep, ArtnPauliAdjointInfo &info) {
-  if (!d) return fail(ARTN_E_INVALID, "null descriptor");
-  if (int rc = state_max_rank(d->dtype, max_rank, ARTN_PAULI_ADJOINT_MAX_RANK, true, max_rank)) return rc;
-  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ep)) return rc;
-  int64_t flagged = n_steps;
-  if (measure) flagged = std::count_if(measure, measure + n_steps, [](uint8_t f) { return f != 0; });
-  const int64_t groups = std::min<int64_t>(std::max<int64_t>(ep.pl.n >> ARTN_PAULI_TILE_BITS, 1), ARTN_PAULI_EVOLVE_MAX_GRID);
-  info = ArtnPauliAdjointInfo{};
-  info.n_runs = ep.info.n_runs;
-  info.n_launches = ep.info.n_runs + 1;
-  info.max_rank = ep.info.max_rank;
-  info.n_measured = (int32_t)flagged;
-  info.table_bytes = ep.info.table_bytes;
-  info.workspace_bytes = n_steps * groups * ARTN_PAULI_ADJOINT_WAVES * 2 * (int64_t)sizeof(double);
-  info.bytes_read = 2 * ep.info.bytes_read;
-  info.bytes_written = 2 * ep.info.bytes_written;
+                              PauliAdjointPlan &ap) {
+  if (int rc = run_pair_rank<PauliAdjointFamily>(d, max_rank)) return rc;
+  if (int rc = pauli_evolve_plan(d, ops, n_steps, max_rank, ap.one)) return rc;
+  run_pair_info<PauliAdjointFamily>(ap, measure ? std::count_if(measure, measure + n_steps, [](uint8_t f) { return f != 0; }) : n_steps);
+  ap.info.table_bytes = ap.one.info.table_bytes;
   return ARTN_OK;
-}
-
-template <typename T, int R>
-static hipError_t pauli_adjoint_launch_rank(T *lam, T *phi, long tiles, const ArtnPauliEvolveRun *run, const ArtnPauliEvolveStep *stp,
-                                            double *ws, long groups, hipStream_t st) {
-  const size_t lds = ((size_t)2 * sizeof(T) << ARTN_PAULI_TILE_BITS) << R;
-  if (hipError_t e = ensure_lds<artn_k_pauli_adjoint<T, R>>(lds); e != hipSuccess) return e;
-  const long n_blocks = tiles >> R;
-  const dim3 grid((unsigned)std::min<long>(n_blocks, ARTN_PAULI_EVOLVE_MAX_GRID));
-  hipLaunchKernelGGL((artn_k_pauli_adjoint<T, R>), grid, dim3(ARTN_BORN_THREADS), lds, st, lam, phi, n_blocks, run, stp, ws, groups);
-  return hipSuccess;
-}
-
-template <typename T>
-static hipError_t pauli_adjoint_launch(const PauliEvolvePlan &ep, T *lam, T *phi, const void *table, double *ws, double *out, hipStream_t st) {
-  const ArtnPauliEvolveRun *runs;
-  const ArtnPauliEvolveStep *stp;
-  state_table_parts<ArtnPauliEvolveHeader>(table, ep.runs.size(), runs, stp);
-  const int64_t n = ep.pl.n;
-  const int n_steps = (int)ep.pl.xm.size();
-  const long tiles = (long)std::max<int64_t>(n >> ARTN_PAULI_TILE_BITS, 1);
-  const long groups = std::min<long>(tiles, ARTN_PAULI_EVOLVE_MAX_GRID);
-  if (n < ((int64_t)1 << ARTN_PAULI_TILE_BITS)) {
-    hipLaunchKernelGGL(artn_k_pauli_adjoint_small<T>, dim3(1), dim3(ARTN_BORN_THREADS), 0, st, lam, phi, (long)n, stp, n_steps, ws);
-  } else {
-    for (size_t r = 0; r < ep.runs.size(); ++r) {
-      const hipError_t e = state_with_rank<T, ARTN_PAULI_ADJOINT_MAX_RANK>((int)ep.runs[r].basis.size(), [&](auto rank) {
-        return pauli_adjoint_launch_rank<T, decltype(rank)::value>(lam, phi, tiles, runs + r, stp, ws, groups, st);
-      });
-      if (e != hipSuccess) return e;
-    }
-  }
-  hipLaunchKernelGGL(artn_k_pauli_adjoint_finish, dim3((unsigned)n_steps), dim3(ARTN_BORN_THREADS), 0, st, (const double *)ws, groups, tiles,
-                     stp, out);
-  return hipSuccess;
 }
 
 extern "C" {
@@ -516,20 +456,21 @@ int artn_pauli_adjoint_query(const ArtnMarginalDesc *d, const uint8_t *ops, cons
                              int32_t *slot_mask, int32_t *run_rank, uint64_t *run_basis, int32_t *run_pivot) {
   if (!info) return fail(ARTN_E_INVALID, "null info");
   if (!coeff) return fail(ARTN_E_INVALID, "null pointer");
-  PauliEvolvePlan ep;
-  if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ep, *info)) return rc;
-  pauli_evolve_report(ep, xmask, zmask, n_y, run, slot_mask, run_rank, run_basis, run_pivot);
+  PauliAdjointPlan ap;
+  if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ap)) return rc;
+  *info = ap.info;
+  pauli_evolve_report(ap.one, xmask, zmask, n_y, run, slot_mask, run_rank, run_basis, run_pivot);
   return ARTN_OK;
 }
 
 int artn_pauli_adjoint_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const double *coeff, const uint8_t *measure, int64_t n_steps,
                             int32_t max_rank, void *table, int64_t table_bytes) {
-  PauliEvolvePlan ep;
-  ArtnPauliAdjointInfo info;
-  if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ep, info)) return rc;
+  PauliAdjointPlan ap;
+  if (int rc = pauli_adjoint_plan(d, ops, measure, n_steps, max_rank, ap)) return rc;
   if (!table || !coeff) return fail(ARTN_E_INVALID, "null pointer");
-  if (int rc = state_table_fits(table_bytes, info.table_bytes, "artn_pauli_adjoint_query")) return rc;
+  if (int rc = state_table_fits(table_bytes, ap.info.table_bytes, "artn_pauli_adjoint_query")) return rc;
   if (int rc = state_table_aligned(table, "artn_pauli_adjoint_pack")) return rc;
+  const PauliEvolvePlan &ep = ap.one;
   pauli_evolve_fill(ep, coeff, table);
   ArtnPauliEvolveRun *runs;
   ArtnPauliEvolveStep *stp;
@@ -543,22 +484,9 @@ int artn_pauli_adjoint_pack(const ArtnMarginalDesc *d, const uint8_t *ops, const
 
 int artn_pauli_adjoint(const ArtnMarginalDesc *d, void *lam, void *phi, const uint8_t *ops, int64_t n_steps, int32_t max_rank,
                        const void *table, int64_t table_bytes, void *workspace, int64_t workspace_bytes, double *out, void *stream) {
-  if (artn_device_count() < 1) return fail(ARTN_E_NODEVICE, "no gfx950 device visible");
-  PauliEvolvePlan ep;
-  ArtnPauliAdjointInfo info;
-  if (int rc = pauli_adjoint_plan(d, ops, nullptr, n_steps, max_rank, ep, info)) return rc; // (coefficients and flags are in the table)
-  if (!lam || !phi || !table || !workspace || !out) return fail(ARTN_E_INVALID, "null pointer");
-  if (int rc = state_table_fits(table_bytes, info.table_bytes, "artn_pauli_adjoint_query")) return rc;
-  if (workspace_bytes < info.workspace_bytes) return fail(ARTN_E_INVALID, "workspace smaller than artn_pauli_adjoint_query reports");
-  if ((((uintptr_t)lam | (uintptr_t)phi | (uintptr_t)workspace) & 15) != 0)
-    return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint needs 16-byte aligned arrays and workspace");
-  if ((((uintptr_t)table | (uintptr_t)out) & 7) != 0) return fail(ARTN_E_UNSUPPORTED, "artn_pauli_adjoint needs an 8-byte aligned table and output");
-  if (int rc = state_disjoint(lam, phi, (uintptr_t)ep.pl.n * (d->dtype == ARTN_C64 ? 8 : 16), "artn_pauli_adjoint")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == ARTN_C64) HIP_TRY(pauli_adjoint_launch(ep, (float2 *)lam, (float2 *)phi, table, (double *)workspace, out, st));
-  else HIP_TRY(pauli_adjoint_launch(ep, (double2 *)lam, (double2 *)phi, table, (double *)workspace, out, st));
-  HIP_TRY(hipGetLastError());
-  return ARTN_OK;
+  return run_pair_apply<PauliAdjointFamily>(d, lam, phi, table, table_bytes, workspace, workspace_bytes, out, stream, [&](PauliAdjointPlan &ap) {
+    return pauli_adjoint_plan(d, ops, nullptr, n_steps, max_rank, ap); // (coefficients and flags are in the table)
+  });
 }
 
 } // extern "C"

@@ -3,8 +3,8 @@
 // artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the max_rank rule and the rank dispatch of the run
 // kernels, the matrix scan, the argument checks of the pack / apply entries, the parts of a packed table, the plan, the
 // column packer, the table header and the K dispatch of the tile kernels (wide gates, matrix gates, controlled gates,
-// channels).  The whole host half of the two dense-gate families is artn_dense_gate_host.h, on top of this.  Codes and
-// texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording (`who`: "gate
+// channels).  The whole host half of the two dense-gate families is artn_dense_gate_host.h, what the four run-circuit
+// families share artn_run_circuit_host.h, both on top of this.  Codes and texts are part of the ABI's behaviour (tests/test_state_layout_cpu.py); each family keeps its own wording (`who`: "gate
 // circuits take", ...) and its own precedence between the errors, so the pieces are separate functions.
 #pragma once
 #include <algorithm>

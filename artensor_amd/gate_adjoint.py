@@ -14,16 +14,13 @@ After a call both tensors are bit for bit what apply_gates_ leaves on each alone
 The transition elements are sums in float64 in a fixed order: bit-identical from run to run for one plan; the order follows the
 blocks of the runs, so they may differ in the last bits between max_rank values.  There is no CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native
-from ._state import _Prebuilt, _checked, _desc, _dtype_code, _interleaved, _max_rank, _overlaps, _packed, _ptr
-from .born import norm2, overlap
-from .gates import GateCircuit, _matrix, _split_gates
-from .pauli import PauliSumOperator
+from ._state import _PairCircuit, _checked, _desc, _dtype_code, _interleaved, _max_rank, _ptr, _run_keys, _run_query
+from .adjoint import _adjoint_sweep
+from .gates import _GATE_ARRAYS, GateCircuit, _gate_keys, _matrix, _split_gates
 
 __all__ = ["gate_adjoint_info", "GatePairCircuit", "apply_gates_pair_", "gate_adjoint_gradient", "parametric_gate"]
 
@@ -47,19 +44,8 @@ def _split_measure(measure, k):
 
 
 def _pair_query(d, k, dims, mat, mmat, flags, max_rank, arrays=False):
-    n = k.shape[0]
-    info = _native.ArtnGatesAdjointInfo()
-    if arrays:
-        bits = np.zeros((n, 2), dtype=np.int32)
-        run, slot, local, rank = (np.zeros(n, dtype=np.int32) for _ in range(4))
-        pivot = np.zeros((n, _native.GATES_MAX_RANK), dtype=np.int32)
-        out = (bits, run, slot, local, rank, pivot)
-        ptrs = [_ptr(x) for x in out]
-    else:
-        out, ptrs = (), [None] * 6
-    _native.check(_native.lib().artn_gates_adjoint_query(ctypes.byref(d), _ptr(k), _ptr(dims), _ptr(mat), _ptr(mmat), _ptr(flags), n,
-                                                         max_rank, ctypes.byref(info), *ptrs))
-    return (info,) + out
+    return _run_query("artn_gates_adjoint_query", _native.ArtnGatesAdjointInfo(), d, (k, dims, mat, mmat, flags), max_rank, _GATE_ARRAYS,
+                      arrays)
 
 
 def gate_adjoint_info(shape, strides, gates, dtype=torch.complex64, measure=None, max_rank=None):
@@ -70,18 +56,11 @@ def gate_adjoint_info(shape, strides, gates, dtype=torch.complex64, measure=None
     _dtype_code(dtype, "gate_adjoint_info")
     k, dims, mat = _split_gates(gates, len(shape))
     flags, mmat = _split_measure(measure, k)
-    info, bits, run, slot, local, rank, pivot = _pair_query(_desc(shape, strides, dtype), k, dims, mat, mmat, flags, _max_rank(max_rank),
-                                                            arrays=True)
-    nr = info.n_runs
-    ranks = [int(v) for v in rank[:nr]]
-    return {"bits": [tuple(int(b) for b in bits[g, :k[g]]) for g in range(len(k))], "run": [int(v) for v in run],
-            "slot_mask": [int(v) for v in slot], "local": [bool(v) for v in local], "measure": [bool(f) for f in flags],
-            "n_measured": info.n_measured, "n_runs": nr, "n_launches": info.n_launches, "max_rank": info.max_rank, "run_rank": ranks,
-            "run_pivot": [[int(v) for v in pivot[r, :ranks[r]]] for r in range(nr)], "table_bytes": info.table_bytes,
-            "workspace_bytes": info.workspace_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written}
+    info, *per_gate, rank, pivot = _pair_query(_desc(shape, strides, dtype), k, dims, mat, mmat, flags, _max_rank(max_rank), arrays=True)
+    return {**_gate_keys(k, *per_gate), "measure": [bool(f) for f in flags], **_run_keys(info, rank, run_pivot=pivot)}
 
 
-class GatePairCircuit(_Prebuilt):
+class GatePairCircuit(_PairCircuit):
     """The gates of a GateCircuit for TWO tensors of one layout: validates, cuts the runs, packs the table and copies it to
     `device` once; the workspace is allocated per call, so an instance holds no state that two calls share.  measure: None (no
     gate is measured) or one entry per gate, None or a matrix M of the gate's size (any matrix).  circ(lam, phi, device=False)
@@ -90,33 +69,17 @@ class GatePairCircuit(_Prebuilt):
     host synchronisation."""
 
     def __init__(self, shape, strides, dtype, gates, device, measure=None, max_rank=None):
-        self._bind(shape, strides, dtype, device)
-        self._k, self._dims, mat = _split_gates(gates, len(self.shape))
-        flags, mmat = _split_measure(measure, self._k)
-        self._d = _desc(self.shape, self.strides, dtype)
-        self._max_rank = _max_rank(max_rank)
-        table, info = _packed(_pair_query(self._d, self._k, self._dims, mat, mmat, flags, self._max_rank)[0],
-                              lambda *table: _native.lib().artn_gates_adjoint_pack(ctypes.byref(self._d), _ptr(self._k), _ptr(self._dims),
-                                                                                   _ptr(mat), _ptr(mmat), _ptr(flags), self._k.shape[0],
-                                                                                   self._max_rank, *table))
-        self.n_gates, self.n_runs, self.max_rank, self.n_measured = self._k.shape[0], info.n_runs, info.max_rank, info.n_measured
-        self.table_bytes, self.workspace_bytes = info.table_bytes, info.workspace_bytes
-        self._upload(table)
+        def split(n_dims):
+            k, dims, mat = _split_gates(gates, n_dims)
+            flags, mmat = _split_measure(measure, k)
+            return k, dims, mat, mmat, flags
+
+        (self._k, self._dims, *_), info = self._build(shape, strides, dtype, device, max_rank, split, _pair_query,
+                                                      "artn_gates_adjoint_pack")
+        self.n_gates, self.n_measured = self._n, info.n_measured
 
     def __call__(self, lam, phi, device=False):
-        what = "gate_adjoint.GatePairCircuit"
-        for x in (lam, phi):
-            self._check(x, what)
-        if _overlaps(lam, phi):
-            raise ValueError(f"{what}: lam overlaps phi")
-        out = torch.empty((self.n_gates, 2), dtype=torch.float64, device=phi.device)
-        ws = torch.empty(self.workspace_bytes // 8, dtype=torch.float64, device=phi.device)   # (per call: calls may overlap on streams)
-        with torch.cuda.device(phi.device):
-            _native.check(_native.lib().artn_gates_adjoint(ctypes.byref(self._d), lam.data_ptr(), phi.data_ptr(), _ptr(self._k),
-                                                           _ptr(self._dims), self.n_gates, self._max_rank, self._table.data_ptr(),
-                                                           self.table_bytes, ws.data_ptr(), self.workspace_bytes, out.data_ptr(),
-                                                           _native.current_stream_ptr(phi.device)))
-        return out if device else out.cpu().numpy().view(np.complex128).reshape(self.n_gates)
+        return self._run("gate_adjoint.GatePairCircuit", "artn_gates_adjoint", lam, phi, device, _ptr(self._k), _ptr(self._dims))
 
 
 def apply_gates_pair_(lam, phi, gates, measure=None, max_rank=None, device=False):
@@ -202,21 +165,8 @@ def gate_adjoint_gradient(amps0, gates, terms, params=None, normalize=True, max_
         if len(params) != n_par or any(p < -1 for p in params):
             raise ValueError(f"params: one integer >= -1 per parametrised gate expected ({n_par})")
     back_measure = [m if s is not None and params[s] >= 0 else None for m, s in zip(back_measure, slot)]
-    shape, strides, dtype, dev = amps0.shape, amps0.stride(), amps0.dtype, amps0.device
+    layout = (amps0.shape, amps0.stride(), amps0.dtype)
     # built first: max_rank follows the two-state limits, and a refusal comes before any work on the device
-    sweep = GatePairCircuit(shape, strides, dtype, back[::-1], dev, back_measure[::-1], max_rank)
-    phi = torch.empty_strided(shape, strides, dtype=dtype, device=dev)
-    phi.copy_(amps0)
-    GateCircuit(shape, strides, dtype, forward, dev, max_rank)(phi)
-    lam = PauliSumOperator(shape, strides, dtype, terms, dev)(phi)
-    energy = overlap(phi, lam)[0].real
-    t = sweep(lam, phi)
-    grad = np.zeros(max(params) + 1 if params else 0, dtype=np.float64)
-    n_gates = len(gates)
-    for g, s in enumerate(slot):
-        if s is not None and params[s] >= 0:
-            grad[params[s]] += 2.0 * t[n_gates - 1 - g].real
-    if normalize:
-        n2 = norm2(amps0)
-        energy, grad = energy / n2, grad / n2
-    return energy, grad
+    sweep = GatePairCircuit(*layout, back[::-1], amps0.device, back_measure[::-1], max_rank)
+    return _adjoint_sweep(amps0, lambda: GateCircuit(*layout, forward, amps0.device, max_rank), sweep, terms,
+                          [-1 if s is None else params[s] for s in slot], lambda t: 2.0 * t.real, normalize)

@@ -13,13 +13,11 @@ pauli.py takes -- a dense GPU tensor of complex64 or complex128 -- and keep its 
 formed in float64 in one fixed order and rounded once, so the result is bit for bit independent of where the runs are cut.  There
 is no CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native
-from ._state import _Prebuilt, _checked, _desc, _dtype_code, _interleaved, _max_rank, _packed, _ptr
+from ._state import _RunCircuit, _checked, _desc, _dtype_code, _interleaved, _max_rank, _ptr, _run_keys, _run_pack, _run_query
 
 __all__ = ["apply_gates_", "apply_gate_", "GateCircuit", "gate_circuit_info", "gates_from_bonds", "run_circuit", "merge_gates"]
 
@@ -53,19 +51,18 @@ def _split_gates(gates, n_dims):
     return k, np.ascontiguousarray(dims), mat
 
 
+# what a circuit query writes: bits, run, slot_mask, local, run_rank, run_pivot
+_GATE_ARRAYS = ((np.int32, 2),) + ((np.int32, 0),) * 4 + ((np.int32, _native.GATES_MAX_RANK),)
+
+
 def _gates_query(d, k, dims, mat, max_rank, arrays=False):
-    n = k.shape[0]
-    info = _native.ArtnGatesInfo()
-    if arrays:
-        bits = np.zeros((n, 2), dtype=np.int32)
-        run, slot, local, rank = (np.zeros(n, dtype=np.int32) for _ in range(4))
-        pivot = np.zeros((n, _native.GATES_MAX_RANK), dtype=np.int32)
-        out = (bits, run, slot, local, rank, pivot)
-        ptrs = [_ptr(x) for x in out]
-    else:
-        out, ptrs = (), [None] * 6
-    _native.check(_native.lib().artn_gates_query(ctypes.byref(d), _ptr(k), _ptr(dims), _ptr(mat), n, max_rank, ctypes.byref(info), *ptrs))
-    return (info,) + out
+    return _run_query("artn_gates_query", _native.ArtnGatesInfo(), d, (k, dims, mat), max_rank, _GATE_ARRAYS, arrays)
+
+
+def _gate_keys(k, bits, run, slot, local):
+    """The per-gate lists of gate_circuit_info."""
+    return {"bits": [tuple(int(b) for b in bits[g, :k[g]]) for g in range(len(k))], "run": [int(v) for v in run],
+            "slot_mask": [int(v) for v in slot], "local": [bool(v) for v in local]}
 
 
 def gate_circuit_info(shape, strides, gates, dtype=torch.complex64, max_rank=None):
@@ -75,44 +72,28 @@ def gate_circuit_info(shape, strides, gates, dtype=torch.complex64, max_rank=Non
     table_bytes, bytes_read = bytes_written = n_runs * bytes of the state."""
     _dtype_code(dtype, "gate_circuit_info")
     k, dims, mat = _split_gates(gates, len(shape))
-    info, bits, run, slot, local, rank, pivot = _gates_query(_desc(shape, strides, dtype), k, dims, mat, _max_rank(max_rank), arrays=True)
-    nr = info.n_runs
-    ranks = [int(v) for v in rank[:nr]]
-    return {"bits": [tuple(int(b) for b in bits[g, :k[g]]) for g in range(len(k))], "run": [int(v) for v in run],
-            "slot_mask": [int(v) for v in slot], "local": [bool(v) for v in local], "n_runs": nr, "n_launches": info.n_launches,
-            "max_rank": info.max_rank, "run_rank": ranks, "run_pivot": [[int(v) for v in pivot[r, :ranks[r]]] for r in range(nr)],
-            "table_bytes": info.table_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written}
+    info, *per_gate, rank, pivot = _gates_query(_desc(shape, strides, dtype), k, dims, mat, _max_rank(max_rank), arrays=True)
+    return {**_gate_keys(k, *per_gate), **_run_keys(info, rank, run_pivot=pivot)}
 
 
 def _gates_pack(d, k, dims, mat, max_rank):
     """The circuit table (include/artn.h) as a uint8 numpy array."""
-    return _packed(_gates_query(d, k, dims, mat, max_rank)[0],
-                   lambda *table: _native.lib().artn_gates_pack(ctypes.byref(d), _ptr(k), _ptr(dims), _ptr(mat), k.shape[0], max_rank,
-                                                                *table))
+    return _run_pack(_gates_query, "artn_gates_pack", d, (k, dims, mat), max_rank)
 
 
-class GateCircuit(_Prebuilt):
+class GateCircuit(_RunCircuit):
     """An ordered list of gates [(matrix, dims), ...] for tensors of one layout.  Validates, cuts the runs, packs the table and
     copies it to `device` once; circ(amps) then updates amps IN PLACE with one launch per run and returns it.  max_rank: a run
     holds blocks of up to 2^max_rank tiles of 2^10 elements in LDS (None: 64 KiB per workgroup; 0: one launch per gate with a
     target above the tile; a two-qubit gate on two such targets always gets a block of four tiles)."""
 
     def __init__(self, shape, strides, dtype, gates, device, max_rank=None):
-        self._bind(shape, strides, dtype, device)
-        self._k, self._dims, mat = _split_gates(gates, len(self.shape))
-        self._d = _desc(self.shape, self.strides, dtype)
-        self._max_rank = _max_rank(max_rank)
-        table, info = _gates_pack(self._d, self._k, self._dims, mat, self._max_rank)
-        self.n_gates, self.n_runs, self.max_rank, self.table_bytes = self._k.shape[0], info.n_runs, info.max_rank, info.table_bytes
-        self._upload(table)
+        (self._k, self._dims, _), _ = self._build(shape, strides, dtype, device, max_rank, lambda nd: _split_gates(gates, nd), _gates_query,
+                                                  "artn_gates_pack")
+        self.n_gates = self._n
 
     def __call__(self, amps):
-        self._check(amps, "gates.GateCircuit")
-        with torch.cuda.device(amps.device):
-            _native.check(_native.lib().artn_gates_apply(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._k), _ptr(self._dims), None,
-                                                         self.n_gates, self._max_rank, self._table.data_ptr(), self.table_bytes,
-                                                         _native.current_stream_ptr(amps.device)))
-        return amps
+        return self._run("gates.GateCircuit", "artn_gates_apply", amps, _ptr(self._k), _ptr(self._dims), None)   # (mat: in the table)
 
 
 def apply_gates_(amps, gates, max_rank=None):

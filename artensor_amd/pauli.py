@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _native
-from ._state import _Prebuilt, _checked, _desc, _dtype_code, _max_rank, _overlaps, _packed, _ptr
+from ._state import (_Prebuilt, _RunCircuit, _checked, _desc, _dtype_code, _max_rank, _overlaps, _packed, _ptr, _run_keys, _run_pack,
+                     _run_query)
 from .born import norm2, overlap
 
 __all__ = ["pauli_ops", "pauli_info", "pauli_expectation", "pauli_sum_expectation", "pauli_apply_info", "PauliSumOperator",
@@ -269,20 +270,19 @@ def _split_steps(steps, n_dims):
     return np.ascontiguousarray(coeff), ops
 
 
+# what a circuit query writes: xmask, zmask, n_y, run, slot_mask, run_rank, run_basis, run_pivot
+_STEP_ARRAYS = ((np.uint64, 0),) * 2 + ((np.int32, 0),) * 4 + tuple((t, _native.PAULI_EVOLVE_MAX_RANK) for t in (np.uint64, np.int32))
+
+
 def _evolve_query(d, ops, coeff, max_rank, arrays=False):
-    n = ops.shape[0]
-    info = _native.ArtnPauliEvolveInfo()
-    if arrays:
-        xm, zm = (np.zeros(n, dtype=np.uint64) for _ in range(2))
-        ny, run, slot, rank = (np.zeros(n, dtype=np.int32) for _ in range(4))
-        basis = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.uint64)
-        pivot = np.zeros((n, _native.PAULI_EVOLVE_MAX_RANK), dtype=np.int32)
-        out = (xm, zm, ny, run, slot, rank, basis, pivot)
-        ptrs = [_ptr(x) for x in out]
-    else:
-        out, ptrs = (), [None] * 8
-    _native.check(_native.lib().artn_pauli_evolve_query(ctypes.byref(d), _ptr(ops), _ptr(coeff), n, max_rank, ctypes.byref(info), *ptrs))
-    return (info,) + out
+    return _run_query("artn_pauli_evolve_query", _native.ArtnPauliEvolveInfo(), d, (ops, coeff), max_rank, _STEP_ARRAYS, arrays)
+
+
+def _step_keys(coeff, xm, zm, ny, run, slot):
+    """The per-step lists of pauli_evolve_info."""
+    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny],
+            "alpha": [complex(c[0], c[1]) for c in coeff], "beta": [complex(c[2], c[3]) for c in coeff],
+            "run": [int(v) for v in run], "slot_mask": [int(v) for v in slot]}
 
 
 def pauli_evolve_info(shape, strides, steps, dtype=torch.complex64, max_rank=None):
@@ -292,48 +292,28 @@ def pauli_evolve_info(shape, strides, steps, dtype=torch.complex64, max_rank=Non
     state."""
     _dtype_code(dtype, "pauli_evolve_info")
     coeff, ops = _split_steps(steps, len(shape))
-    info, xm, zm, ny, run, slot, rank, basis, pivot = _evolve_query(_desc(shape, strides, dtype), ops, coeff, _max_rank(max_rank),
-                                                                    arrays=True)
-    nr = info.n_runs
-    ranks = [int(v) for v in rank[:nr]]
-    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny],
-            "alpha": [complex(c[0], c[1]) for c in coeff], "beta": [complex(c[2], c[3]) for c in coeff],
-            "run": [int(v) for v in run], "slot_mask": [int(v) for v in slot], "n_runs": nr, "n_launches": info.n_launches,
-            "max_rank": info.max_rank, "run_rank": ranks,
-            "run_basis": [[int(v) for v in basis[r, :ranks[r]]] for r in range(nr)],
-            "run_pivot": [[int(v) for v in pivot[r, :ranks[r]]] for r in range(nr)],
-            "table_bytes": info.table_bytes, "bytes_read": info.bytes_read, "bytes_written": info.bytes_written}
+    info, *steps, rank, basis, pivot = _evolve_query(_desc(shape, strides, dtype), ops, coeff, _max_rank(max_rank), arrays=True)
+    return {**_step_keys(coeff, *steps), **_run_keys(info, rank, run_basis=basis, run_pivot=pivot)}
 
 
 def _evolve_pack(d, ops, coeff, max_rank):
     """The circuit table (include/artn.h) as a uint8 numpy array."""
-    return _packed(_evolve_query(d, ops, coeff, max_rank)[0],
-                   lambda *table: _native.lib().artn_pauli_evolve_pack(ctypes.byref(d), _ptr(ops), _ptr(coeff), ops.shape[0], max_rank,
-                                                                       *table))
+    return _run_pack(_evolve_query, "artn_pauli_evolve_pack", d, (ops, coeff), max_rank)
 
 
-class PauliCircuit(_Prebuilt):
+class PauliCircuit(_RunCircuit):
     """An ordered list of steps a <- alpha a + beta P a for tensors of one layout: steps = [(theta, string), ...] for the rotation
     exp(-i theta P) or (alpha, beta, string) for the general step.  Validates, cuts the runs, packs the table and copies it to
     `device` once; circ(amps) then updates amps IN PLACE with one launch per run and returns it.  max_rank: a run holds blocks of
     up to 2^max_rank tiles of 2^10 elements in LDS (None: 64 KiB per workgroup; 0: one launch per step with a flip above the tile)."""
 
     def __init__(self, shape, strides, dtype, steps, device, max_rank=None):
-        self._bind(shape, strides, dtype, device)
-        coeff, self._ops = _split_steps(steps, len(self.shape))
-        self._d = _desc(self.shape, self.strides, dtype)
-        self._max_rank = _max_rank(max_rank)
-        table, info = _evolve_pack(self._d, self._ops, coeff, self._max_rank)
-        self.n_steps, self.n_runs, self.max_rank, self.table_bytes = self._ops.shape[0], info.n_runs, info.max_rank, info.table_bytes
-        self._upload(table)
+        (self._ops, _), _ = self._build(shape, strides, dtype, device, max_rank, lambda nd: _split_steps(steps, nd)[::-1], _evolve_query,
+                                        "artn_pauli_evolve_pack")
+        self.n_steps = self._n
 
     def __call__(self, amps):
-        self._check(amps, "pauli.PauliCircuit")
-        with torch.cuda.device(amps.device):
-            _native.check(_native.lib().artn_pauli_evolve(ctypes.byref(self._d), amps.data_ptr(), _ptr(self._ops), self.n_steps,
-                                                          self._max_rank, self._table.data_ptr(), self.table_bytes,
-                                                          _native.current_stream_ptr(amps.device)))
-        return amps
+        return self._run("pauli.PauliCircuit", "artn_pauli_evolve", amps, _ptr(self._ops))
 
 
 def pauli_evolve_(amps, steps, max_rank=None):
