@@ -163,6 +163,17 @@ from .channel import (  # noqa: F401
     phase_damping,
     phase_flip,
 )
+from . import trajectories  # noqa: F401
+from .trajectories import (  # noqa: F401
+    BatchChannelOp,
+    channel_batch_,
+    collapse_batch_,
+    measure_batch_,
+    postselect_batch_,
+    reset_batch_,
+    trajectory_info,
+    trajectory_norms,
+)
 from . import diagonal  # noqa: F401
 from .diagonal import (  # noqa: F401
     DiagonalOperator,

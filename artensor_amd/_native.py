@@ -302,6 +302,33 @@ class ArtnChannelInfo(ctypes.Structure):
     ]
 
 
+BATCH_MAX_BITS, BATCH_MAX_FIELDS = 24, 24
+
+
+class ArtnBatchInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_fields", ctypes.c_int32),
+        ("batch_bits", ctypes.c_int32),
+        ("tile_bits", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("launches", ctypes.c_int32),
+        ("reset_launches", ctypes.c_int32),
+        ("B", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("n", ctypes.c_int64),
+        ("n_tiles", ctypes.c_int64),
+        ("segment", ctypes.c_int64),
+        ("lds_bytes", ctypes.c_int64),
+        ("table_bytes", ctypes.c_int64),
+        ("record_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("bytes_written", ctypes.c_int64),
+        ("field_shift", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_width", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_pos", ctypes.c_int32 * BATCH_MAX_FIELDS),
+    ]
+
+
 DIAG_MAX_GROUPS, DIAG_MAX_TERMS, DIAG_TILE_BITS = 64, 65536, 10
 DIAG_PHASE, DIAG_MULTIPLY = 0, 1
 DIAG_PAIR_EVOLVE, DIAG_PAIR_TRANSITION = 0, 1
@@ -507,6 +534,25 @@ _EXPORTS = {
     "artn_channel_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_void_p]),
+    # additive to ABI 9 as well: batched trajectories -- measurement, reset and channels per state (has("artn_channel_batch_apply"))
+    "artn_measure_batch_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.POINTER(ArtnBatchInfo)]),
+    "artn_measure_batch_choose": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_measure_batch_collapse": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                   ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "artn_channel_batch_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.POINTER(ArtnBatchInfo), ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_channel_batch_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int64]),
+    "artn_channel_batch_choose": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    "artn_channel_batch_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
     # additive to ABI 9 as well: diagonal operators -- cost-function phases, moments and pairs in one pass (has("artn_diag_apply"))
     "artn_diag_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.POINTER(ArtnDiagInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -1,4 +1,4 @@
-"""What the state modules (adjoint born channel controlled diagonal gate_adjoint gates krylov layout measure pauli rdm wide_gates)
+"""What the state modules (adjoint born channel controlled diagonal gate_adjoint gates krylov layout measure pauli rdm trajectories wide_gates)
 share on the host: the checks of a tensor and of a dtype, the layout descriptor, the marshalling of dims, matrices and packed
 tables, and the base class of the objects that are built once for tensors of one layout.  A family's wrapper writes its argument
 split, its query and pack calls and its apply call; everything else it takes from here.  This module imports no state module.

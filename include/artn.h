@@ -1111,6 +1111,88 @@ int artn_channel_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int3
                        int64_t table_bytes, const void *record, int64_t record_bytes, void *stream);
 
 /*
+ * BATCHED TRAJECTORIES: B states in ONE tensor, measured, reset and sent through noise channels with an outcome, a scale and an
+ * operator PER STATE (additive to ABI 9: has("artn_channel_batch_apply")).  batch_dims[0 .. nb-1] (nb >= 0; NULL where nb == 0)
+ * are distinct dimensions of any power-of-two extent, disjoint from the measured / target dimensions.  TRAJECTORY b is the
+ * mixed-radix integer of their digits, the FIRST listed one the most significant; B is the product of their extents.  Whatever is
+ * indexed by trajectory -- uniforms, forced outcomes, q, records -- is row b of a DEVICE array.  RECORDS are B times the 32 bytes
+ * of artn_measure_choose's record (int64 outcome or j; float64 probability, total, scale), 8-byte aligned.
+ *
+ * LAYOUT RULE of the whole family: every memory bit of a batch dimension lies at or above a 128-byte line (bit 4 for complex64,
+ * bit 3 for complex128), so neither a 16-byte vector nor a line spans two trajectories.  LIMITS: at most ARTN_BATCH_MAX_BITS batch
+ * memory bits; B * D <= 2^24 (D = 2^k outcomes or 2^t rows: what the streaming artn_marginal keeps); k = 1 .. ARTN_MEASURE_MAX_DIMS
+ * measured dimensions; t = 1..5 targets and a trajectory of at least 2^t elements.  nb == 0 is B = 1: the calls then give what
+ * artn_measure_* / artn_channel_* give, bit for bit, and artn_channel_batch_pack writes the table of artn_channel_pack.
+ *
+ * PLAN.  Batch dimensions that are adjacent in memory and in order merge into FIELDS (shift, width, pos): b = OR over the fields
+ * of ((index >> shift) & (2^width - 1)) << pos, at most ARTN_BATCH_MAX_FIELDS of them.
+ *
+ * MEASUREMENT.  dims[0 .. k-1] are the measured dimensions (extent 2, the first listed the most significant digit).
+ * artn_measure_batch_choose: one lane per trajectory; record[b] is bit for bit what artn_measure_choose writes for q[b, :] (q:
+ *   [B][D] float64, what artn_marginal writes for batch_dims then dims) and uniform[b], or, where `forced` is not NULL, for the
+ *   forced outcome forced[b] (int64 [B]; `uniform` is not read then, and a forced[b] outside 0 .. D-1 gives outcome -1).
+ * artn_measure_batch_collapse: the streaming pass of artn_measure_collapse (reset != 0: its move and clear pair); the trajectory
+ *   of a 16-byte vector comes from the batch fields of its index, and outcome, scale and the scale == 1 shortcut from record[b].
+ *   Slice b afterwards is bit for bit what artn_measure_collapse leaves on that slice with record[b]; a trajectory with outcome
+ *   -1 is neither read nor written.
+ *
+ * CHANNELS.  Forms ARTN_CHANNEL_FIXED and ARTN_CHANNEL_DIAGONAL; ARTN_CHANNEL_DENSE needs a reduced density matrix per
+ * trajectory, which does not exist, and is refused (ARTN_E_UNSUPPORTED).  The table is artn_channel_pack's with the tile fields
+ * of its ArtnWgateTable taken from the batch plan: the TILE BITS are the t targets and the lowest other memory bits that are no
+ * batch bits, tile_bits = min(TB, log2 n - batch bits) in all, so a tile lies in one trajectory; n_tiles << tile_bits = n; tile q
+ * starts at q << log2(segment) with a 0 inserted at every tile bit at or above log2(segment), ascending (n_high counts them; only
+ * the first ARTN_WGATE_MAX_K are listed in high_bit, the kernel takes them from its arguments).
+ * artn_channel_batch_choose: one lane per trajectory; record[b] is bit for bit the 32-byte head of artn_channel_choose's record
+ *   for input[b, :] (DIAGONAL: q [B][D]; FIXED: not read) and uniform[b].  No current matrix is written.
+ * artn_channel_batch_apply: ONE launch of the tile kernel of artn_channel_apply.  Per tile it derives b from the tile's first
+ *   element and reads record[b]; where j < 0, j >= m, or operator j is a flagged identity and scale == 1.0 it leaves the tile
+ *   before its first access to the state; otherwise every coefficient is mats[j][e] * scale, one float64 multiply, under the
+ *   table's OR block_mask (a coefficient that is exactly zero is left out term by term, so the bits are those of operator j's own
+ *   mask).  Slice b afterwards is bit for bit what artn_wgate_apply gives for K_j * scale; skipped tiles keep every bit.
+ * Everything runs on `stream` with the caller's buffers: no allocation, copy, synchronisation or atomics.
+ *
+ * ARTN_E_INVALID: a batch dimension out of range, repeated, or also measured / a target; a trajectory below 2^t elements; what
+ * artn_measure_query / artn_channel_query call invalid.  ARTN_E_UNSUPPORTED: a batch bit below the line, more than
+ * ARTN_BATCH_MAX_BITS batch bits, B * D above 2^24, the DENSE form, and the refusals of the unbatched queries.
+ */
+#define ARTN_BATCH_MAX_BITS 24
+#define ARTN_BATCH_MAX_FIELDS 24
+typedef struct ArtnBatchInfo {
+  int32_t n_fields;       /* batch fields after merging                                                          */
+  int32_t batch_bits;     /* log2 B                                                                              */
+  int32_t tile_bits;      /* channels: min(TB, log2 n - batch_bits); measurement: 0                              */
+  int32_t grid;           /* workgroups of the pass over the state                                               */
+  int32_t launches;       /* choose + the pass (2); artn_marginal's come on top where q is needed                */
+  int32_t reset_launches; /* measurement: choose + move + clear (3); channels: 0                                 */
+  int64_t B, D, n;        /* trajectories; outcomes 2^k or rows 2^t; elements of the whole tensor                */
+  int64_t n_tiles, segment, lds_bytes, table_bytes; /* channels (as ArtnChannelInfo's); measurement: 0           */
+  int64_t record_bytes;   /* ARTN_MEASURE_RECORD_BYTES * B                                                       */
+  int64_t bytes_read;     /* nominal: measurement the n / D kept elements, channels the whole tensor             */
+  int64_t bytes_written;  /* nominal: the whole tensor                                                           */
+  int32_t field_shift[ARTN_BATCH_MAX_FIELDS]; /* lowest memory bit of field f (the fields in the order listed)  */
+  int32_t field_width[ARTN_BATCH_MAX_FIELDS];
+  int32_t field_pos[ARTN_BATCH_MAX_FIELDS];   /* lowest bit of b that field f fills                             */
+} ArtnBatchInfo;
+/* Host-only: validates and plans. */
+int artn_measure_batch_query(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims, int32_t nb, const int32_t *batch_dims,
+                             ArtnBatchInfo *info);
+int artn_measure_batch_choose(const double *q, int64_t B, int64_t D, const double *uniform, const int64_t *forced, int32_t renormalize,
+                              void *records, void *stream);
+int artn_measure_batch_collapse(const ArtnMarginalDesc *d, void *a, int32_t k, const int32_t *dims, int32_t nb, const int32_t *batch_dims,
+                                const void *records, int32_t reset, void *stream);
+/* Host-only: validates and plans.  mats may be NULL; target_bits (t entries) and tile_bits (info->tile_bits entries, ascending;
+ * room for 12) may be NULL. */
+int artn_channel_batch_query(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t nb, const int32_t *batch_dims, int32_t m,
+                             int32_t form, const double *mats, ArtnBatchInfo *info, int32_t *target_bits, int32_t *tile_bits);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_channel_batch_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *dims, int32_t nb, const int32_t *batch_dims, int32_t m,
+                            int32_t form, const double *mats, const double *weights, void *table, int64_t table_bytes);
+int artn_channel_batch_choose(const void *table, int64_t table_bytes, int32_t t, int32_t m, int32_t form, const double *input,
+                              const double *uniform, int64_t B, int32_t renormalize, void *records, void *stream);
+int artn_channel_batch_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_t *dims, int32_t nb, const int32_t *batch_dims,
+                             int32_t m, const void *table, int64_t table_bytes, const void *records, void *stream);
+
+/*
  * DIAGONAL OPERATORS: a classical cost function f(i) = sum_k c_k (-1)^popcount(i & zmask_k) applied as ONE object, one streaming
  * pass per operation whatever the number of terms (additive to ABI 9: has("artn_diag_apply")).  Descriptor, `ops` (uint8
  * [n_terms][n_dims], I and Z only: codes 0 and 3), masks and layout refusals are those of artn_pauli_query in the wording
