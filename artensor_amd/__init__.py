@@ -166,8 +166,12 @@ from .channel import (  # noqa: F401
 from . import trajectories  # noqa: F401
 from .trajectories import (  # noqa: F401
     BatchChannelOp,
+    BatchConditionalGate,
+    apply_conditional_gate_batch_,
     channel_batch_,
     collapse_batch_,
+    conditional_gate_info,
+    correct_batch_,
     measure_batch_,
     postselect_batch_,
     reset_batch_,

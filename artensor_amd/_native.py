@@ -329,6 +329,24 @@ class ArtnBatchInfo(ctypes.Structure):
     ]
 
 
+CGATE_BATCH_MAX_CASES = 16
+CGATE_CASE_DIAGONAL, CGATE_CASE_IDENTITY = 1, 2
+CGATE_BATCH_CASES_BYTES = 400
+
+
+class ArtnCgateBatchInfo(ctypes.Structure):
+    _fields_ = ArtnCgateInfo._fields_ + [
+        ("m", ctypes.c_int32),
+        ("batch_bits", ctypes.c_int32),
+        ("n_fields", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("B", ctypes.c_int64),
+        ("field_shift", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_width", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_pos", ctypes.c_int32 * BATCH_MAX_FIELDS),
+    ]
+
+
 DIAG_MAX_GROUPS, DIAG_MAX_TERMS, DIAG_TILE_BITS = 64, 65536, 10
 DIAG_PHASE, DIAG_MULTIPLY = 0, 1
 DIAG_PAIR_EVOLVE, DIAG_PAIR_TRANSITION = 0, 1
@@ -553,6 +571,19 @@ _EXPORTS = {
     "artn_channel_batch_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    # additive to ABI 9 as well: conditional gates -- a controlled gate chosen per trajectory by a device-side selector
+    # (has("artn_cgate_batch_apply"))
+    "artn_cgate_batch_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.POINTER(ArtnCgateBatchInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_cgate_batch_pack": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "artn_cgate_batch_apply": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_void_p]),
     # additive to ABI 9 as well: diagonal operators -- cost-function phases, moments and pairs in one pass (has("artn_diag_apply"))
     "artn_diag_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.POINTER(ArtnDiagInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

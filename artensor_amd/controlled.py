@@ -90,9 +90,8 @@ def _control_values(control_values, c, what):
     return np.array(values + [0] * (c == 0), dtype=np.int32)
 
 
-def _split(matrix, targets, controls, control_values, n_dims, what):
-    """(t, int32 targets, c, int32 controls, int32 values, float64 mat [2 * 4^t]); a t the library does not take keeps a zero
-    matrix, so that the library refuses it."""
+def _split_dims(targets, controls, control_values, n_dims, what):
+    """(t, int32 targets, c, int32 controls, int32 values): the arrays have one entry where there is no target or no control."""
     targets = _dims(targets, n_dims)
     controls = _dims(() if controls is None else controls, n_dims)
     t, c = int(targets.shape[0]), int(controls.shape[0])
@@ -100,10 +99,15 @@ def _split(matrix, targets, controls, control_values, n_dims, what):
     if both:
         raise ValueError(f"{what}: dims {both} are listed as targets and as controls")
     values = _control_values(control_values, c, what)
-    if c == 0:
-        controls = np.zeros(1, dtype=np.int32)
+    return t, (targets if t else np.zeros(1, dtype=np.int32)), c, (controls if c else np.zeros(1, dtype=np.int32)), values
+
+
+def _split(matrix, targets, controls, control_values, n_dims, what):
+    """(t, int32 targets, c, int32 controls, int32 values, float64 mat [2 * 4^t]); a t the library does not take keeps a zero
+    matrix, so that the library refuses it."""
+    t, targets, c, controls, values = _split_dims(targets, controls, control_values, n_dims, what)
     if not 1 <= t <= _native.WGATE_MAX_K:
-        return t, (targets if t else np.zeros(1, dtype=np.int32)), c, controls, values, np.zeros(2, dtype=np.float64)
+        return t, targets, c, controls, values, np.zeros(2, dtype=np.float64)
     return t, targets, c, controls, values, _interleaved(_matrix(matrix, t, what))
 
 

@@ -38,49 +38,16 @@ static int batch_plan(const ArtnMarginalDesc *d, int32_t k, const int32_t *dims,
     seen.push_back(dims[j]);
     bp.dim_bit.push_back(__builtin_ctzll((uint64_t)d->stride[dims[j]]));
   }
-  const int lb = d->dtype == ARTN_C64 ? 4 : 3; // index bits of a 128-byte line
-  int low_dim = -1, low_bit = 0;
-  // the fields, the last listed dimension first: it fills the lowest bits of b
-  std::vector<int> shift, width, pos;
-  for (int i = 0; i < nb; ++i) {
-    const int32_t dim = batch_dims[i];
-    if (dim < 0 || dim >= d->n_dims) return fail(ARTN_E_INVALID, "batch dimension " + std::to_string(dim) + " out of range");
-    for (size_t s = 0; s < seen.size(); ++s)
-      if (seen[s] == dim) {
-        if (s < (size_t)k)
-          return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " is both a batch dimension and a " + role + " one");
-        return fail(ARTN_E_INVALID, "the batch dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
-      }
-    seen.push_back(dim);
-  }
-  for (int i = nb - 1; i >= 0; --i) {
-    const int32_t dim = batch_dims[i];
-    if (d->extent[dim] == 1) continue; // (no index bit)
-    const int e = __builtin_ctzll((uint64_t)d->extent[dim]), s = __builtin_ctzll((uint64_t)d->stride[dim]);
-    if (s < lb && (low_dim < 0 || s < low_bit)) low_dim = dim, low_bit = s;
-    if (!shift.empty() && s == shift.back() + width.back() && bp.batch_bits == pos.back() + width.back()) {
-      width.back() += e; // adjacent in memory and in order: one field
-    } else {
-      shift.push_back(s), width.push_back(e), pos.push_back(bp.batch_bits);
-    }
-    bp.batch_bits += e;
-    bp.batch_mask |= (((uint64_t)1 << e) - 1) << s;
-  }
-  if (low_dim >= 0)
-    return fail(ARTN_E_UNSUPPORTED, "batch dimension " + std::to_string(low_dim) + " holds memory bit " + std::to_string(low_bit) +
-                                        ", below a 128-byte line (bit " + std::to_string(lb) +
-                                        " of this dtype): a line would span two trajectories -- move it up with artn_bitperm_apply (relayout_)");
-  if (bp.batch_bits > ARTN_BATCH_MAX_BITS)
-    return fail(ARTN_E_UNSUPPORTED, "at most " + std::to_string(ARTN_BATCH_MAX_BITS) + " batch bits; these dimensions have " +
-                                        std::to_string(bp.batch_bits));
+  BatchDims bd;
+  if (int rc = state_batch_dims(d, nb, batch_dims, seen, (size_t)k, role, bd)) return rc;
+  bp.batch_bits = bd.bits, bp.batch_mask = bd.mask;
   if (bp.batch_bits + k > 24)
     return fail(ARTN_E_UNSUPPORTED, "B * D = 2^" + std::to_string(bp.batch_bits + k) + " is above 2^24, what the streaming marginal keeps");
-  bp.fields.n = (int32_t)shift.size();
+  bp.fields.n = (int32_t)bd.shift.size();
   ArtnBatchInfo &bi = bp.info;
-  for (size_t f = 0; f < shift.size(); ++f) { // (listed order: the most significant field first)
-    const size_t g = shift.size() - 1 - f;
-    bp.fields.shift[f] = shift[g], bp.fields.width[f] = width[g], bp.fields.pos[f] = pos[g];
-    bi.field_shift[f] = shift[g], bi.field_width[f] = width[g], bi.field_pos[f] = pos[g];
+  for (size_t f = 0; f < bd.shift.size(); ++f) { // (listed order: the most significant field first)
+    bp.fields.shift[f] = bd.shift[f], bp.fields.width[f] = bd.width[f], bp.fields.pos[f] = bd.pos[f];
+    bi.field_shift[f] = bd.shift[f], bi.field_width[f] = bd.width[f], bi.field_pos[f] = bd.pos[f];
   }
   bp.elem = d->dtype == ARTN_C64 ? 8 : 16;
   bi.n_fields = bp.fields.n, bi.batch_bits = bp.batch_bits;

@@ -10,61 +10,25 @@
 #include "artn_host.h"
 #include "artn_state_host.h"
 #include "artn_cgate_kernel.h"
-
-struct CgatePlan : TilePlan {
-  int t = 0, c = 0, n_bits = 0;
-  std::vector<int> control; // memory bits in the order listed
-  std::vector<int> value;   // the wanted digit of each control
-  std::vector<int> hole;    // hole bits, ascending
-  uint64_t high_mask = 0, high_want = 0, low_mask = 0, low_want = 0; // over memory bits
-  ArtnCgateInfo info = {};
-};
+#include "artn_cgate_host.h"
 
 // The layout checks of artn_wgate_query, then targets, controls, their classes, the tile and the holes (include/artn.h: PLAN).
 // `mat` may be null (artn_cgate_apply: the matrix is in the table); the flag "diagonal" is then not set.
 static int cgate_plan(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
                       const int32_t *values, const double *mat, CgatePlan &cp) {
-  if (int rc = state_desc(d, "controlled gates take", ARTN_MARG_MAX_DIMS, false)) return rc;
-  if (!targets || (c > 0 && !controls)) return fail(ARTN_E_INVALID, "null pointer");
-  StateLayout l;
-  if (int rc = state_layout(d, l)) return rc;
-  if (int rc = state_bits_only(l, "controlled gates take")) return rc;
-  const int64_t n = l.n;
-  if (t < 1 || t > ARTN_WGATE_MAX_K)
-    return fail(ARTN_E_UNSUPPORTED, "controlled gates act on one to five target dimensions, not " + std::to_string(t));
-  if (c < 0) return fail(ARTN_E_INVALID, "a negative number of controls: " + std::to_string(c));
-  const int n_bits = __builtin_ctzll((uint64_t)n);
+  int64_t n = 0;
+  if (int rc = cgate_head(d, t, targets, c, controls, "controlled gates take", "controlled gates", cp, n)) return rc;
+  const int n_bits = cp.n_bits;
   if (t > n_bits)
     return fail(ARTN_E_INVALID, "a gate on " + std::to_string(t) + " dimensions needs a state of at least 2^" + std::to_string(t) +
                                     " elements; this one has " + std::to_string((long long)n));
-  cp.t = t, cp.c = c, cp.n_bits = n_bits;
-  const int lb = d->dtype == ARTN_C64 ? 4 : 3; // index bits of a 128-byte line
   std::vector<int32_t> seen;
-  for (int j = 0; j < t; ++j) {
-    if (int rc = state_tile_dim(d, targets[j], seen, (size_t)t, false, "gates")) return rc;
-    seen.push_back(targets[j]);
-    cp.target.push_back(__builtin_ctzll((uint64_t)d->stride[targets[j]]));
-  }
-  int c_high = 0;
-  for (int j = 0; j < c; ++j) {
-    if (int rc = state_tile_dim(d, controls[j], seen, (size_t)t, true, "gates")) return rc;
-    seen.push_back(controls[j]);
-    const int v = values ? values[j] : 1;
-    if (v != 0 && v != 1)
-      return fail(ARTN_E_INVALID, "a control value is 0 or 1; control " + std::to_string(j) + " has " + std::to_string(v));
-    const int b = __builtin_ctzll((uint64_t)d->stride[controls[j]]);
-    cp.control.push_back(b), cp.value.push_back(v);
-    if (b >= lb) cp.high_mask |= (uint64_t)1 << b, cp.high_want |= (uint64_t)v << b, ++c_high;
-    else cp.low_mask |= (uint64_t)1 << b, cp.low_want |= (uint64_t)v << b;
-  }
+  if (int rc = cgate_dims(d, targets, controls, values, cp, seen)) return rc;
+  const int c_high = cp.c_high;
   bool diagonal = false;
   if (mat && !state_matrix_scan(mat, 1 << t, diagonal)) return fail(ARTN_E_INVALID, "a matrix entry is not finite");
   state_tile_plan(d->dtype, n_bits - c_high, cp.high_mask, cp);
-  for (int j = cp.seg_bits; j < cp.tb; ++j) cp.hole.push_back(cp.tile[j]);
-  for (int b = 0; b < n_bits; ++b)
-    if ((cp.high_mask >> b) & 1) cp.hole.push_back(b);
-  std::sort(cp.hole.begin(), cp.hole.end());
-  if ((int)cp.hole.size() > ARTN_CGATE_MAX_HOLES) return fail(ARTN_E_UNSUPPORTED, "controlled gates take at most 2^40 elements");
+  if (int rc = cgate_holes(cp, "controlled gates take")) return rc;
   cp.info.t = t, cp.info.c = c, cp.info.c_high = c_high, cp.info.c_low = c - c_high;
   cp.info.tile_bits = cp.tb, cp.info.diagonal = diagonal ? 1 : 0;
   cp.info.n_selected = n >> c, cp.info.n_tiles = cp.n_tiles, cp.info.segment = cp.segment, cp.info.lds_bytes = cp.lds_bytes;
@@ -110,17 +74,9 @@ int artn_cgate_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets
   if (int rc = state_table_fits(table_bytes, cp.info.table_bytes, "artn_cgate_query")) return rc;
   if (int rc = state_table_aligned(table, "artn_cgate_pack")) return rc;
   ArtnCgateTable tab = {};
-  const int rows = 1 << t, gb = cp.tb - t;
-  tab.t = (uint64_t)t, tab.tile_bits = (uint64_t)cp.tb, tab.n_tiles = (uint64_t)cp.info.n_tiles, tab.segment = (uint64_t)cp.info.segment;
-  tab.flags = cp.info.diagonal ? ARTN_GATE_DIAGONAL : 0, tab.group_bits = (uint64_t)gb, tab.segment_bits = (uint64_t)cp.seg_bits;
-  tab.n_holes = (uint64_t)cp.hole.size(), tab.high_want = cp.high_want, tab.high_mask = cp.high_mask;
-  for (size_t j = 0; j < cp.hole.size(); ++j) tab.hole_bit[j] = (uint64_t)cp.hole[j];
-  state_tile_cols(cp, tab.mem_col, tab.lds_col, tab.target_bit, tab.target_pos, tab.swizzle);
-  for (int p = 0; p < cp.tb; ++p) // a low control is a non-target tile bit, so a group bit: the one its lds_col names
-    if ((cp.low_mask >> cp.tile[p]) & 1) {
-      tab.group_mask |= tab.lds_col[p];
-      if ((cp.low_want >> cp.tile[p]) & 1) tab.group_want |= tab.lds_col[p];
-    }
+  const int rows = 1 << t;
+  cgate_tile_fields(cp, tab);
+  tab.flags = cp.info.diagonal ? ARTN_GATE_DIAGONAL : 0;
   tab.block_mask = state_block_mask(mat, rows);
   *(ArtnCgateTable *)table = tab;
   std::copy(mat, mat + 2 * rows * rows, (double *)((ArtnCgateTable *)table + 1));

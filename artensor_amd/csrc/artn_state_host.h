@@ -1,6 +1,6 @@
 // artn_state_host.h -- host plumbing shared by the operations on a dense amplitude array (artn_born.hip, artn_rdm.hip,
 // artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_mgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip,
-// artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the max_rank rule and the rank dispatch of the run
+// artn_batch.hip, artn_cgate_batch.hip, artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the batch dimensions, the max_rank rule and the rank dispatch of the run
 // kernels, the matrix scan, the argument checks of the pack / apply entries, the parts of a packed table, the plan, the
 // column packer, the table header and the K dispatch of the tile kernels (wide gates, matrix gates, controlled gates,
 // channels).  The whole host half of the two dense-gate families is artn_dense_gate_host.h, what the four run-circuit
@@ -176,6 +176,59 @@ static int state_tile_targets(const ArtnMarginalDesc *d, int32_t k, const int32_
     seen.push_back(dims[j]);
     target.push_back(__builtin_ctzll((uint64_t)d->stride[dims[j]]));
   }
+  return ARTN_OK;
+}
+
+// ---- batch dimensions: B trajectories in one tensor (include/artn.h: BATCHED TRAJECTORIES) ----
+
+struct BatchDims {
+  int bits = 0;      // log2 B
+  uint64_t mask = 0; // over memory bits
+  std::vector<int> shift, width, pos; // the fields, the most significant one first (the order listed)
+};
+
+// The nb batch dimensions against `seen`, the dimensions listed before them: its first k are `role` ones ("measured", "target"),
+// the rest controls.  What is wrong with them (ARTN_E_INVALID) before what the layout does not support: a batch bit below a
+// 128-byte line, more than ARTN_BATCH_MAX_BITS batch bits.  Dimensions adjacent in memory and in order merge into one field.
+static int state_batch_dims(const ArtnMarginalDesc *d, int32_t nb, const int32_t *batch_dims, std::vector<int32_t> &seen, size_t k,
+                            const char *role, BatchDims &bd) {
+  const size_t listed = seen.size();
+  const int lb = d->dtype == ARTN_C64 ? 4 : 3; // index bits of a 128-byte line
+  for (int i = 0; i < nb; ++i) {
+    const int32_t dim = batch_dims[i];
+    if (dim < 0 || dim >= d->n_dims) return fail(ARTN_E_INVALID, "batch dimension " + std::to_string(dim) + " out of range");
+    for (size_t s = 0; s < seen.size(); ++s)
+      if (seen[s] == dim) {
+        if (s < k)
+          return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " is both a batch dimension and a " + role + " one");
+        if (s < listed) return fail(ARTN_E_INVALID, "dimension " + std::to_string(dim) + " is both a batch dimension and a control one");
+        return fail(ARTN_E_INVALID, "the batch dimensions must differ; dimension " + std::to_string(dim) + " is repeated");
+      }
+    seen.push_back(dim);
+  }
+  int low_dim = -1, low_bit = 0;
+  std::vector<int> shift, width, pos; // the last listed dimension first: it fills the lowest bits of b
+  for (int i = nb - 1; i >= 0; --i) {
+    const int32_t dim = batch_dims[i];
+    if (d->extent[dim] == 1) continue; // (no index bit)
+    const int e = __builtin_ctzll((uint64_t)d->extent[dim]), s = __builtin_ctzll((uint64_t)d->stride[dim]);
+    if (s < lb && (low_dim < 0 || s < low_bit)) low_dim = dim, low_bit = s;
+    if (!shift.empty() && s == shift.back() + width.back() && bd.bits == pos.back() + width.back()) {
+      width.back() += e; // adjacent in memory and in order: one field
+    } else {
+      shift.push_back(s), width.push_back(e), pos.push_back(bd.bits);
+    }
+    bd.bits += e;
+    bd.mask |= (((uint64_t)1 << e) - 1) << s;
+  }
+  if (low_dim >= 0)
+    return fail(ARTN_E_UNSUPPORTED, "batch dimension " + std::to_string(low_dim) + " holds memory bit " + std::to_string(low_bit) +
+                                        ", below a 128-byte line (bit " + std::to_string(lb) +
+                                        " of this dtype): a line would span two trajectories -- move it up with artn_bitperm_apply (relayout_)");
+  if (bd.bits > ARTN_BATCH_MAX_BITS)
+    return fail(ARTN_E_UNSUPPORTED, "at most " + std::to_string(ARTN_BATCH_MAX_BITS) + " batch bits; these dimensions have " +
+                                        std::to_string(bd.bits));
+  bd.shift.assign(shift.rbegin(), shift.rend()), bd.width.assign(width.rbegin(), width.rend()), bd.pos.assign(pos.rbegin(), pos.rend());
   return ARTN_OK;
 }
 

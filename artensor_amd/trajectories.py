@@ -15,6 +15,9 @@ they are.  Here every trajectory gets its own outcome or Kraus operator:
     BatchChannelOp     one trajectory step of a Channel (FIXED or DIAGONAL form) on every slice: operator j[b] drawn with
                        probability w_j / sum_j w_j from uniforms[b], K_j * scale applied to slice b; channel_batch_ builds one per call
     trajectory_norms   sum |amps|^2 of every slice, [B]
+    BatchConditionalGate  a controlled gate chosen per trajectory from a table of at most 16 cases by an int64 per trajectory in
+                       device memory -- the outcomes above, where they lie (C ABI: artn_cgate_batch_query / _pack / _apply);
+                       apply_conditional_gate_batch_ builds one per call, correct_batch_ is the X / Z correction by two bits
 
 Slice b afterwards is bit for bit what the unbatched call leaves on that slice with record[b]: measure.collapse_ for the
 measurements, apply_wide_gate_(slice, K_j * scale) for the channels.  A trajectory where nothing can be observed or drawn
@@ -35,13 +38,16 @@ import numpy as np
 import torch
 
 from . import _native
-from ._state import _Prebuilt, _checked, _dense_layout, _desc, _dims, _dtype_code, _lib, _packed, _ptr
+from ._state import _Prebuilt, _checked, _dense_layout, _desc, _dims, _dtype_code, _interleaved, _lib, _packed, _ptr
 from .born import marginal_probabilities
 from .channel import Channel, _split
+from .controlled import _split_dims
+from .gates import _matrix
 from .measure import _dims as _measured_dims
 
 __all__ = ["measure_batch_", "postselect_batch_", "reset_batch_", "collapse_batch_", "BatchChannelOp", "channel_batch_",
-           "trajectory_info", "trajectory_norms"]
+           "trajectory_info", "trajectory_norms", "BatchConditionalGate", "apply_conditional_gate_batch_", "conditional_gate_info",
+           "correct_batch_"]
 
 _KERNELS = ("artn_channel_batch_apply", "batched-trajectory kernels")   # what _lib looks for, and what it calls them
 _LINE_BIT = {torch.complex64: 4, torch.complex128: 3}                   # index bits of a 128-byte line
@@ -261,6 +267,171 @@ def channel_batch_(amps, channel, dims, batch_dims, uniforms=None, generator=Non
     _checked(amps, "trajectories.channel_batch_")
     return BatchChannelOp(amps.shape, amps.stride(), amps.dtype, channel, dims, batch_dims, amps.device)(amps, uniforms, generator,
                                                                                                          renormalize)
+
+
+# ---- conditional gates: a controlled gate chosen per trajectory by a device-side selector -------------------------------------------
+_CGATE_KERNELS = ("artn_cgate_batch_apply", "conditional-gate kernels")
+
+
+def _integer(v, name, what):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{what}: {name} must be an integer, got {v!r}")
+    v = int(v)
+    if not 0 <= v < 2 ** 63:
+        raise ValueError(f"{what}: {name} must lie in 0 .. 2^63 - 1, got {v}")
+    return v
+
+
+def _cases(cases, t, mask, what):
+    """(int64 keys [m], float64 mats [m * 2 * 4^t], mask as the library takes it).  The number of cases, repeated keys and keys
+    outside the mask are the library's to refuse; a t it does not take keeps zero matrices, so that it refuses t."""
+    pairs = list(cases.items()) if isinstance(cases, dict) else [tuple(p) for p in cases]
+    if any(len(p) != 2 for p in pairs):
+        raise ValueError(f"{what}: cases is a dict {{key: matrix}} or a list of (key, matrix) pairs")
+    keys = np.array([_integer(k, "a key", what) for k, _ in pairs] + [0] * (not pairs), dtype=np.int64)
+    if 1 <= t <= _native.WGATE_MAX_K and pairs:
+        mats = np.concatenate([_interleaved(_matrix(u, t, what)) for _, u in pairs])
+    else:
+        mats = np.zeros(max(len(pairs), 1) * 2, dtype=np.float64)
+    return len(pairs), keys, mats, -1 if mask is None else _integer(mask, "mask", what)
+
+
+def _cgate_plan(shape, strides, dtype, cases, targets, batch_dims, controls, control_values, mask, what, arrays=False):
+    _dtype_code(dtype, what)
+    nd = len(shape)
+    t, targets, c, controls, values = _split_dims(targets, controls, control_values, nd, what)
+    batch = _dims(() if batch_dims is None else batch_dims, nd)
+    m, keys, mats, mask = _cases(cases, t, mask, what)
+    d, info = _desc(shape, strides, dtype), _native.ArtnCgateBatchInfo()
+    target, control, tile = (np.full(n, -1, dtype=np.int32) for n in (_native.WGATE_MAX_K, max(c, 1), 12))
+    _native.check(_lib(*_CGATE_KERNELS, what).artn_cgate_batch_query(
+        ctypes.byref(d), t, _ptr(targets), c, _ptr(controls), _ptr(values), batch.shape[0], _ptr(batch) if batch.shape[0] else None, m,
+        _ptr(keys), mask, _ptr(mats), None, 1, ctypes.byref(info), _ptr(target) if arrays else None, _ptr(control) if arrays else None,
+        _ptr(tile) if arrays else None))
+    return d, (t, targets, c, controls, values, batch), (m, keys, mats, mask), info, (target, control, tile)
+
+
+def conditional_gate_info(shape, strides, cases, targets, batch_dims, controls=(), control_values=None, dtype=torch.complex64, mask=None):
+    """Host-only: the plan of one conditional gate.  The keys of controlled_gate_info (t, c, c_high / c_low, target_bits,
+    control_bits, control_values, tile_bits ascending, tb, n_selected, n_tiles with n_tiles << tb == n >> c_high, segment, lds_bytes,
+    table_bytes, nominal bytes, diagonal: every case is) and m, keys, B, batch_bits, fields (as trajectory_info's), grid."""
+    what = "conditional_gate_info"
+    _, (t, _, c, _, values, _), (m, keys, _, _), info, (target, control, tile) = _cgate_plan(
+        shape, strides, dtype, cases, targets, batch_dims, controls, control_values, mask, what, arrays=True)
+    return {"t": info.t, "c": info.c, "c_high": info.c_high, "c_low": info.c_low,
+            "target_bits": tuple(int(b) for b in target[:t]), "control_bits": tuple(int(b) for b in control[:c]),
+            "control_values": tuple(int(v) for v in values[:c]), "tile_bits": [int(b) for b in tile[:info.tile_bits]],
+            "tb": info.tile_bits, "n_selected": info.n_selected, "n_tiles": info.n_tiles, "segment": info.segment,
+            "lds_bytes": info.lds_bytes, "table_bytes": info.table_bytes, "bytes_read": info.bytes_read,
+            "bytes_written": info.bytes_written, "diagonal": bool(info.diagonal), "m": info.m, "keys": tuple(int(k) for k in keys[:m]),
+            "B": info.B, "batch_bits": info.batch_bits,
+            "fields": [(int(info.field_shift[f]), int(info.field_width[f]), int(info.field_pos[f])) for f in range(info.n_fields)],
+            "grid": info.grid}
+
+
+def _selector(selector, B, device, what):
+    """(address, stride in 8-byte words) of the B selector words; host-only checks, the tensor is never read."""
+    if not isinstance(selector, torch.Tensor):
+        raise TypeError(f"{what}: the selector is a GPU tensor, got {type(selector).__name__}")
+    if not selector.is_cuda:
+        raise RuntimeError(f"{what}: the selector must live on the GPU (got a {selector.device} tensor); there is no CPU fallback")
+    if selector.device != device:
+        raise ValueError(f"{what}: the selector lives on {selector.device}, the amplitudes on {device}")
+    words = _native.MEASURE_RECORD_BYTES // 8
+    if selector.dtype == torch.float64:
+        if selector.dim() != 2 or tuple(selector.shape) != (B, words) or selector.stride(1) != 1:
+            raise ValueError(f"{what}: a float64 selector is the [{B}, {words}] records of collapse_batch_ / BatchChannelOp.step, got "
+                             f"shape {tuple(selector.shape)}, strides {tuple(selector.stride())}")
+        stride = selector.stride(0) if B > 1 else words
+    elif selector.dtype == torch.int64:
+        if selector.dim() > 1 or selector.numel() != B:
+            raise ValueError(f"{what}: the selector is an int64 GPU tensor of {B} elements, one per trajectory, got shape "
+                             f"{tuple(selector.shape)}")
+        stride = selector.stride(0) if B > 1 else 1
+    else:
+        raise TypeError(f"{what}: an int64 selector (or the float64 records of collapse_batch_) expected, got {selector.dtype}")
+    if stride < 1:
+        raise ValueError(f"{what}: a selector stride of at least one 8-byte word is needed, not {stride}")
+    if selector.data_ptr() % 8:
+        raise ValueError(f"{what}: the selector must start on an 8-byte boundary")
+    return selector.data_ptr(), int(stride)
+
+
+class BatchConditionalGate(_Prebuilt):
+    """A gate chosen per trajectory, for tensors of one layout.  `cases` is a dict {key: matrix} or a list of (key, matrix) pairs,
+    1 to 16 of them: distinct integer keys in 0 .. 2^63 - 1 inside `mask` (None: all bits), each matrix complex [2^t, 2^t] on
+    `targets` (t = 1..5, the first listed dim the most significant digit, as apply_wide_gate_); controls / control_values as
+    ControlledGate's; batch_dims as the rest of this module's, disjoint from targets and controls.  Validates, plans, packs the
+    table and copies it to `device` once.
+
+    g(amps, selector) then updates amps IN PLACE with ONE launch and returns it.  `selector` holds one int64 per trajectory on
+    the GPU: an int64 tensor of B elements with any stride (the view records.view(torch.int64)[:, 0] that measure_batch_ returns
+    is read where it lies), or the float64 [B, 4] records of collapse_batch_ / BatchChannelOp.step.  With o = selector[b]:
+    o < 0, no case with key == (o & mask), or a case that is exactly the identity leave trajectory b untouched -- no tile of it
+    is read or written; otherwise slice b becomes bit for bit what apply_controlled_gate_ leaves on a dense clone of it for that
+    case's matrix.  The host never reads the selector."""
+
+    def __init__(self, shape, strides, dtype, cases, targets, batch_dims, device, controls=(), control_values=None, mask=None):
+        what = "BatchConditionalGate"
+        self._bind(shape, strides, dtype, device)
+        self._d, split, (self.m, keys, mats, self._mask), info, _ = _cgate_plan(self.shape, self.strides, dtype, cases, targets, batch_dims,
+                                                                                controls, control_values, mask, what)
+        self.t, self._targets, self.c, self._controls, self._values, self._batch = split
+        self.keys, self.mask = tuple(int(k) for k in keys[:self.m]), mask
+        self.B, self.tile_bits, self.n_tiles, self.grid, self.table_bytes = info.B, info.tile_bits, info.n_tiles, info.grid, info.table_bytes
+        self.c_high, self.c_low = info.c_high, info.c_low
+        self.batch_dims = tuple(int(x) for x in self._batch)
+        self._upload(_packed(info, lambda *table: _lib(*_CGATE_KERNELS, what).artn_cgate_batch_pack(
+            ctypes.byref(self._d), self.t, _ptr(self._targets), self.c, _ptr(self._controls), _ptr(self._values), self._batch.shape[0],
+            _ptr(self._batch) if self._batch.shape[0] else None, self.m, _ptr(keys), self._mask, _ptr(mats), *table))[0])
+
+    def _upload(self, table):
+        # (pinned and non-blocking, as BatchChannelOp's: apply_conditional_gate_batch_ builds an object per call)
+        self._table = torch.from_numpy(table).pin_memory().to(self.device, non_blocking=True)
+
+    def __call__(self, amps, selector):
+        what = "trajectories.BatchConditionalGate"
+        self._check(amps, what)
+        sel, stride = _selector(selector, self.B, amps.device, what)
+        with torch.cuda.device(amps.device):
+            _native.check(_lib(*_CGATE_KERNELS, what).artn_cgate_batch_apply(
+                ctypes.byref(self._d), amps.data_ptr(), self.t, _ptr(self._targets), self.c, _ptr(self._controls), _ptr(self._values),
+                self._batch.shape[0], _ptr(self._batch) if self._batch.shape[0] else None, self.m, self._table.data_ptr(),
+                self.table_bytes, sel, stride, self._mask, _native.current_stream_ptr(amps.device)))
+        return amps
+
+
+def apply_conditional_gate_batch_(amps, cases, targets, batch_dims, selector, controls=(), control_values=None, mask=None):
+    """amps <- for every trajectory b the case of `cases` that selector[b] names, on `targets` under `controls`, in place: one
+    launch; returns amps.  (Plans and uploads per call: build a BatchConditionalGate once to apply the same cases repeatedly.)"""
+    _checked(amps, "trajectories.apply_conditional_gate_batch_")
+    return BatchConditionalGate(amps.shape, amps.stride(), amps.dtype, cases, targets, batch_dims, amps.device, controls, control_values,
+                                mask)(amps, selector)
+
+
+_PAULI_X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
+_PAULI_Z = np.diag([1.0, -1.0]).astype(np.complex128)
+
+
+def correct_batch_(amps, target, batch_dims, selector, x_bit=None, z_bit=None):
+    """The Pauli correction of teleportation and of active reset, per trajectory and in one launch: with o = selector[b], X on
+    `target` where bit x_bit of o is set, THEN Z where bit z_bit is set (the matrix Z^z X^x; the mask is the two bits, the cases
+    the four products, the identity among them, which leaves its trajectories untouched).  x_bit or z_bit None: no such
+    correction.  A trajectory with o < 0 is untouched.  Applied twice with one selector it gives back the input bit for bit where
+    at most one of the two bits is set, and its negative where both are: (ZX)^2 = -1."""
+    what = "trajectories.correct_batch_"
+    bits = [None if b is None else _integer(b, name, what) for b, name in ((x_bit, "x_bit"), (z_bit, "z_bit"))]
+    if bits[0] is None and bits[1] is None:
+        raise ValueError(f"{what}: x_bit or z_bit is needed")
+    if bits[0] == bits[1] or any(b is not None and b > 62 for b in bits):
+        raise ValueError(f"{what}: x_bit and z_bit are different bits 0 .. 62 of the selector, got {x_bit} and {z_bit}")
+    cases = {}
+    for x in range(1 if bits[0] is None else 2):
+        for z in range(1 if bits[1] is None else 2):
+            key = (x << bits[0] if x else 0) | (z << bits[1] if z else 0)
+            cases[key] = np.linalg.matrix_power(_PAULI_Z, z) @ np.linalg.matrix_power(_PAULI_X, x)
+    mask = sum(1 << b for b in bits if b is not None)
+    return apply_conditional_gate_batch_(amps, cases, (target,), batch_dims, selector, mask=mask)
 
 
 def trajectory_norms(amps, batch_dims):

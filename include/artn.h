@@ -1193,6 +1193,92 @@ int artn_channel_batch_apply(const ArtnMarginalDesc *d, void *a, int32_t t, cons
                              int32_t m, const void *table, int64_t table_bytes, const void *records, void *stream);
 
 /*
+ * CONDITIONAL GATES on batched trajectories: a controlled gate CHOSEN PER TRAJECTORY from a table of cases by an int64 in device
+ * memory, in place, in one launch (additive to ABI 9: has("artn_cgate_batch_apply")).  targets, controls and control_values are
+ * those of artn_cgate_query, batch_dims those of the batched trajectories above (disjoint from targets and controls, every batch
+ * bit at or above a 128-byte line, at most ARTN_BATCH_MAX_BITS of them; nb == 0 is B = 1).  The m (1 .. ARTN_CGATE_BATCH_MAX_CASES)
+ * CASES are keys[j], distinct integers in 0 .. 2^63 - 1, and mats[j], float64 [m][2 * 4^t], each the 2^t x 2^t matrix of
+ * artn_wgate_query on the targets (any finite matrix).  mask is -1 (all bits) or lies in 0 .. 2^63 - 1, and every key lies inside it.
+ *
+ * SELECTOR.  B int64 words in DEVICE memory, word b at selector + 8 * b * selector_stride bytes (8-byte aligned, stride >= 1):
+ * a contiguous int64 [B] has stride 1, the records of artn_measure_batch_choose / artn_channel_batch_choose stride 4.  The host
+ * never reads it.
+ *
+ * CONTRACT.  For trajectory b, o = selector[b].  o < 0 (the -1 of a dead trajectory): untouched.  Otherwise key = o & mask and j
+ * is the case with keys[j] == key; no such case: untouched; mats[j] exactly the identity (1.0 on the diagonal, zeros of either sign
+ * elsewhere): untouched.  Otherwise slice b becomes bit for bit what artn_cgate_apply leaves on a dense copy of that slice for
+ * mats[j], the targets, the controls and the control values.  UNTOUCHED: every bit is kept and no tile of the trajectory is read or
+ * written -- non-finite data, NaN payloads and the sign of a zero included.  So nb == 0 with one case is artn_cgate_apply under
+ * the condition (cond = selector, cond_mask = mask, cond_value = keys[0]) bit for bit, and one case without controls under a
+ * selector that matches everywhere is artn_wgate_apply bit for bit.  Everything runs on `stream` with the caller's buffers: no
+ * allocation, copy, synchronisation or atomics; results are bit-identical from run to run.
+ *
+ * PLAN.  That of artn_cgate_query on an index space without the batch bits: the TILE BITS are the t targets and the lowest memory
+ * bits that are neither targets, high controls nor batch bits, tile_bits = min(TB, log2 n - c_high - batch_bits) in all, so a tile
+ * lies in one trajectory and holds none of its high controls; n_tiles = 2^(log2 n - c_high - tile_bits).  The HOLES are the tile
+ * bits at or above log2(segment) and the high controls; the batch bits are walked by the tile number like any other free bit.
+ * Per tile the kernel derives b from the tile's first element by the batch FIELDS, loads selector[b], and leaves the tile before
+ * its first access to the state where the trajectory is untouched.  A low control lies below a line and a batch bit at or above
+ * it, so the group mask of artn_cgate_apply is unchanged.
+ *
+ * TABLE (8-byte little-endian fields): ArtnCgateTable (flags and block_mask: the AND of the "diagonal" flags, the OR of the masks),
+ * ArtnCgateBatchCases, then the m matrices as float64 (Re, Im), row-major.  table_bytes = 1000 + 400 + m * 16 * 4^t.
+ *
+ * ARTN_E_INVALID: what artn_cgate_query calls invalid; a batch dimension out of range, repeated, or also a target or a control; m
+ * outside 1 .. 16; a key below 0, repeated, or outside the mask; a mask below -1; a matrix entry that is not finite; t + c above
+ * the index bits of a trajectory (a trajectory below 2^t elements once the controls are taken out); a selector stride below 1.
+ * ARTN_E_UNSUPPORTED: what artn_cgate_query does not support; a batch bit below the line; more than ARTN_BATCH_MAX_BITS batch bits;
+ * a selector that is not 8-byte aligned.
+ */
+#define ARTN_CGATE_BATCH_MAX_CASES 16
+#define ARTN_CGATE_CASE_DIAGONAL 1 /* ArtnCgateBatchCases.flags: every off-diagonal entry is exactly 0 */
+#define ARTN_CGATE_CASE_IDENTITY 2 /* ... the matrix is exactly the identity                           */
+typedef struct ArtnCgateBatchCases {
+  uint64_t m;
+  uint64_t reserved;
+  int64_t key[ARTN_CGATE_BATCH_MAX_CASES];         /* entries at and above m: -1, which no masked selector equals */
+  uint64_t flags[ARTN_CGATE_BATCH_MAX_CASES];
+  uint64_t block_mask[ARTN_CGATE_BATCH_MAX_CASES]; /* as ArtnWgateTable's, per case                               */
+} ArtnCgateBatchCases;
+typedef struct ArtnCgateBatchInfo {
+  int32_t t, c;
+  int32_t c_high, c_low;
+  int32_t tile_bits;     /* min(TB, log2 n - c_high - batch_bits)                         */
+  int32_t diagonal;      /* 1: every off-diagonal entry of every case is exactly 0        */
+  int64_t n_selected;    /* n >> c: the elements whose control digits match               */
+  int64_t n_tiles;       /* n_tiles << tile_bits = n >> c_high                            */
+  int64_t segment;       /* elements of a contiguous segment of a tile                    */
+  int64_t lds_bytes;
+  int64_t table_bytes;
+  int64_t bytes_read;    /* nominal: (n >> c_high) elements, every trajectory touched     */
+  int64_t bytes_written;
+  int32_t m;             /* cases                                                         */
+  int32_t batch_bits;    /* log2 B                                                        */
+  int32_t n_fields;      /* batch fields after merging                                    */
+  int32_t grid;          /* workgroups of the launch                                      */
+  int64_t B;             /* trajectories                                                  */
+  int32_t field_shift[ARTN_BATCH_MAX_FIELDS]; /* as ArtnBatchInfo's */
+  int32_t field_width[ARTN_BATCH_MAX_FIELDS];
+  int32_t field_pos[ARTN_BATCH_MAX_FIELDS];
+} ArtnCgateBatchInfo;
+/* Host-only: validates and plans.  keys and mats may be NULL (not checked then); selector may be NULL (its alignment is not
+ * checked then; selector_stride always is); target_bits (t entries), control_bits (c entries) and tile_bits (info->tile_bits
+ * entries, ascending; room for 12) may be NULL. */
+int artn_cgate_batch_query(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
+                           const int32_t *control_values, int32_t nb, const int32_t *batch_dims, int32_t m, const int64_t *keys,
+                           int64_t mask, const double *mats, const void *selector, int64_t selector_stride, ArtnCgateBatchInfo *info,
+                           int32_t *target_bits, int32_t *control_bits, int32_t *tile_bits);
+/* Host-only: writes the table into HOST memory (8-byte aligned, at least table_bytes of the query). */
+int artn_cgate_batch_pack(const ArtnMarginalDesc *d, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
+                          const int32_t *control_values, int32_t nb, const int32_t *batch_dims, int32_t m, const int64_t *keys,
+                          int64_t mask, const double *mats, void *table, int64_t table_bytes);
+/* The chosen gates on `a`, in place: ONE launch on `stream`.  `table` is DEVICE memory holding what artn_cgate_batch_pack wrote
+ * for the same descriptor, targets, controls, control values, batch dimensions and m.  ARTN_E_NODEVICE without a device. */
+int artn_cgate_batch_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const int32_t *targets, int32_t c, const int32_t *controls,
+                           const int32_t *control_values, int32_t nb, const int32_t *batch_dims, int32_t m, const void *table,
+                           int64_t table_bytes, const void *selector, int64_t selector_stride, int64_t mask, void *stream);
+
+/*
  * DIAGONAL OPERATORS: a classical cost function f(i) = sum_k c_k (-1)^popcount(i & zmask_k) applied as ONE object, one streaming
  * pass per operation whatever the number of terms (additive to ABI 9: has("artn_diag_apply")).  Descriptor, `ops` (uint8
  * [n_terms][n_dims], I and Z only: codes 0 and 3), masks and layout refusals are those of artn_pauli_query in the wording
