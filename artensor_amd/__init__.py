@@ -173,9 +173,13 @@ from .trajectories import (  # noqa: F401
     conditional_gate_info,
     correct_batch_,
     measure_batch_,
+    pauli_batch_info,
+    pauli_expectation_batch,
+    pauli_sum_expectation_batch,
     postselect_batch_,
     reset_batch_,
     trajectory_info,
+    trajectory_mean,
     trajectory_norms,
 )
 from . import diagonal  # noqa: F401

@@ -347,6 +347,29 @@ class ArtnCgateBatchInfo(ctypes.Structure):
     ]
 
 
+class ArtnPauliBatchInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_groups", ctypes.c_int32),
+        ("n_launches", ctypes.c_int32),
+        ("terms_per_launch", ctypes.c_int32),
+        ("batch_bits", ctypes.c_int32),
+        ("local_bits", ctypes.c_int32),
+        ("tile_bits", ctypes.c_int32),
+        ("n_fields", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("chunks", ctypes.c_int64),
+        ("chunks_halved", ctypes.c_int64),
+        ("B", ctypes.c_int64),
+        ("n", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("out_bytes", ctypes.c_int64),
+        ("bytes_read", ctypes.c_int64),
+        ("field_shift", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_width", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_pos", ctypes.c_int32 * BATCH_MAX_FIELDS),
+    ]
+
+
 DIAG_MAX_GROUPS, DIAG_MAX_TERMS, DIAG_TILE_BITS = 64, 65536, 10
 DIAG_PHASE, DIAG_MULTIPLY = 0, 1
 DIAG_PAIR_EVOLVE, DIAG_PAIR_TRANSITION = 0, 1
@@ -584,6 +607,13 @@ _EXPORTS = {
                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                               ctypes.c_int64, ctypes.c_void_p]),
+    # additive to ABI 9 as well: Pauli expectation values per trajectory of a batched tensor (has("artn_pauli_batch_expect"))
+    "artn_pauli_batch_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.POINTER(ArtnPauliBatchInfo), ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "artn_pauli_batch_expect": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_void_p]),
     # additive to ABI 9 as well: diagonal operators -- cost-function phases, moments and pairs in one pass (has("artn_diag_apply"))
     "artn_diag_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.POINTER(ArtnDiagInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

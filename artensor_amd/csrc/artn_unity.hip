@@ -30,5 +30,6 @@
 #include "artn_channel.hip" // (artn_channel_kernel.h)
 #include "artn_batch.hip" // (artn_batch_kernel.h)
 #include "artn_cgate_batch.hip" // (artn_cgate_batch_kernel.h)
+#include "artn_pauli_batch.hip" // (artn_pauli_batch_kernel.h)
 #include "artn_diag.hip" // (artn_diag_kernel.h)
 #include "artn_bitperm.hip" // (artn_bitperm_kernel.h)

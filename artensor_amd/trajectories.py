@@ -18,6 +18,9 @@ they are.  Here every trajectory gets its own outcome or Kraus operator:
     BatchConditionalGate  a controlled gate chosen per trajectory from a table of at most 16 cases by an int64 per trajectory in
                        device memory -- the outcomes above, where they lie (C ABI: artn_cgate_batch_query / _pack / _apply);
                        apply_conditional_gate_batch_ builds one per call, correct_batch_ is the X / Z correction by two bits
+    pauli_expectation_batch  <psi_b|P|psi_b> of every trajectory for up to sixteen strings of equal X/Y positions per pass over the
+                       tensor (C ABI: artn_pauli_batch_query / _expect); pauli_sum_expectation_batch is sum_k c_k <P_k> per
+                       trajectory, trajectory_mean the (weighted) mean over trajectories and its standard error
 
 Slice b afterwards is bit for bit what the unbatched call leaves on that slice with record[b]: measure.collapse_ for the
 measurements, apply_wide_gate_(slice, K_j * scale) for the channels.  A trajectory where nothing can be observed or drawn
@@ -44,10 +47,11 @@ from .channel import Channel, _split
 from .controlled import _split_dims
 from .gates import _matrix
 from .measure import _dims as _measured_dims
+from .pauli import pauli_ops
 
 __all__ = ["measure_batch_", "postselect_batch_", "reset_batch_", "collapse_batch_", "BatchChannelOp", "channel_batch_",
            "trajectory_info", "trajectory_norms", "BatchConditionalGate", "apply_conditional_gate_batch_", "conditional_gate_info",
-           "correct_batch_"]
+           "correct_batch_", "pauli_expectation_batch", "pauli_sum_expectation_batch", "trajectory_mean", "pauli_batch_info"]
 
 _KERNELS = ("artn_channel_batch_apply", "batched-trajectory kernels")   # what _lib looks for, and what it calls them
 _LINE_BIT = {torch.complex64: 4, torch.complex128: 3}                   # index bits of a 128-byte line
@@ -438,3 +442,112 @@ def trajectory_norms(amps, batch_dims):
     """sum |amps|^2 of every trajectory: marginal_probabilities over the batch dims, as a float64 GPU tensor [B]."""
     batch = _dims(() if batch_dims is None else batch_dims, amps.dim())
     return marginal_probabilities(amps, batch.tolist()).reshape(-1)
+
+
+# ---- observables per trajectory ---------------------------------------------------------------------------------------------------
+_PAULI_KERNELS = ("artn_pauli_batch_expect", "batched Pauli-expectation kernels")
+
+
+def _pauli_query(d, ops, batch, what, masks=False):
+    n_terms = ops.shape[0]
+    info = _native.ArtnPauliBatchInfo()
+    out = tuple(np.zeros(n_terms, dtype=t) for t in (np.uint64, np.uint64, np.int32, np.int32, np.uint64, np.uint64)) if masks else ()
+    _native.check(_lib(*_PAULI_KERNELS, what).artn_pauli_batch_query(
+        ctypes.byref(d), _ptr(ops), n_terms, batch.shape[0], _ptr(batch) if batch.shape[0] else None, ctypes.byref(info),
+        *([_ptr(x) for x in out] if masks else [None] * 6)))
+    return (info,) + out
+
+
+def pauli_batch_info(shape, strides, paulis, batch_dims, dtype=torch.complex64):
+    """Host-only: the plan of pauli_expectation_batch.  Per string: xmask, zmask (memory bits), local_xmask, local_zmask (the same
+    compressed onto the bits that are no batch bits), n_y and group.  B, n, batch_bits, local_bits (M), tile_bits = min(10, M),
+    fields (as trajectory_info's); n_groups, n_launches (passes over the tensor, each followed by one finish launch),
+    terms_per_launch; chunks and chunks_halved (the C of a pass whose partner lies inside / outside the tile), grid,
+    workspace_bytes, out_bytes and bytes_read."""
+    what = "pauli_batch_info"
+    _dtype_code(dtype, what)
+    ops, _ = pauli_ops(paulis, len(shape))
+    batch = _dims(() if batch_dims is None else batch_dims, len(shape))
+    info, xm, zm, ny, group, xl, zl = _pauli_query(_desc(shape, strides, dtype), ops, batch, what, masks=True)
+    return {"xmask": [int(v) for v in xm], "zmask": [int(v) for v in zm], "n_y": [int(v) for v in ny], "group": [int(v) for v in group],
+            "local_xmask": [int(v) for v in xl], "local_zmask": [int(v) for v in zl], "n_groups": info.n_groups,
+            "n_launches": info.n_launches, "terms_per_launch": info.terms_per_launch, "B": info.B, "n": info.n,
+            "batch_bits": info.batch_bits, "local_bits": info.local_bits, "tile_bits": info.tile_bits,
+            "fields": [(int(info.field_shift[f]), int(info.field_width[f]), int(info.field_pos[f])) for f in range(info.n_fields)],
+            "chunks": info.chunks, "chunks_halved": info.chunks_halved, "grid": info.grid, "workspace_bytes": info.workspace_bytes,
+            "out_bytes": info.out_bytes, "bytes_read": info.bytes_read}
+
+
+def _pauli_raw(amps, ops, batch_dims, what):
+    """float64 GPU tensor [B, n_terms + 1]: row b holds the raw sums of trajectory b in term order, then its sum |a|^2."""
+    _checked(amps, what)
+    batch = _dims(() if batch_dims is None else batch_dims, amps.dim())
+    d = _desc(amps.shape, amps.stride(), amps.dtype)
+    info = _pauli_query(d, ops, batch, what)[0]
+    n_terms = ops.shape[0]
+    out = torch.empty((info.B, n_terms + 1), dtype=torch.float64, device=amps.device)
+    ws = torch.empty(max(info.workspace_bytes // 8, 1), dtype=torch.float64, device=amps.device)   # (per call: calls may overlap on streams)
+    with torch.cuda.device(amps.device):
+        _native.check(_lib(*_PAULI_KERNELS, what).artn_pauli_batch_expect(
+            ctypes.byref(d), amps.data_ptr(), _ptr(ops), n_terms, batch.shape[0], _ptr(batch) if batch.shape[0] else None,
+            out.data_ptr(), ws.data_ptr(), info.workspace_bytes, _native.current_stream_ptr(amps.device)))
+    return out
+
+
+def pauli_expectation_batch(amps, paulis, batch_dims, normalize=True):
+    """<psi_b|P|psi_b> of every trajectory b for one Pauli string or a list of them (written as for pauli_expectation; I on every
+    batch dim).  Returns (values, norms) on the device: values float64 [B, n_terms] ([B] for one string), divided by norms[b]
+    unless normalize=False; norms float64 [B], sum |amps|^2 of every trajectory from the same call.  A trajectory of norm 0 gives
+    NaN under normalize=True (0 / 0: nothing is checked on the host).  Strings of equal X/Y positions share a pass over the
+    tensor, sixteen at a time.  batch_dims=() is B = 1: row 0 holds pauli_expectation(..., normalize=False)'s raw values bit for
+    bit; so does row b of a batched call against a dense clone of slice b whenever a trajectory has at least 2^10 elements and
+    B * (elements of a trajectory / 2^10) <= 2048 (pauli_batch_info: chunks == local tiles)."""
+    what = "trajectories.pauli_expectation_batch"
+    _native.require_gpu(amps, what)
+    ops, single = pauli_ops(paulis, amps.dim())
+    out = _pauli_raw(amps, ops, batch_dims, what)
+    vals, norms = out[:, :-1], out[:, -1]
+    if normalize:
+        vals = vals / norms[:, None]
+    return (vals[:, 0] if single else vals), norms
+
+
+def pauli_sum_expectation_batch(amps, terms, batch_dims, normalize=True):
+    """sum_k c_k <P_k> of every trajectory for terms = [(c_k, string_k), ...] with REAL coefficients: one call of the library and
+    one float64 matmul on the device.  Returns (E float64 [B], norms float64 [B])."""
+    what = "trajectories.pauli_sum_expectation_batch"
+    _native.require_gpu(amps, what)
+    terms = list(terms)
+    if not terms:
+        raise ValueError(f"{what}: at least one term is needed")
+    coeffs = [complex(c) for c, _ in terms]
+    if any(c.imag != 0.0 for c in coeffs):
+        raise ValueError(f"{what}: real coefficients expected (a Hermitian sum); take real and imaginary parts in two calls")
+    vals, norms = pauli_expectation_batch(amps, [p for _, p in terms], batch_dims, normalize)
+    c = torch.from_numpy(np.array([c.real for c in coeffs], dtype=np.float64)).pin_memory().to(amps.device, non_blocking=True)
+    return vals @ c, norms
+
+
+def trajectory_mean(values, weights=None):
+    """(mean, standard error) over dim 0 of `values` ([B] or [B, n_terms]), on the device of `values`, torch only.  weights=None:
+    the mean and std(ddof=1) / sqrt(B).  weights w (a floating tensor [B]: the norms of trajectories kept unnormalised with
+    renormalize=False): sum w v / sum w and sqrt(sum w^2 (v - mean)^2) / sum w; a row with w == 0 is left out even where its value
+    is NaN."""
+    what = "trajectories.trajectory_mean"
+    if not isinstance(values, torch.Tensor) or not values.is_floating_point() or values.dim() < 1:
+        raise TypeError(f"{what}: values is a floating tensor [B] or [B, n_terms]")
+    B = values.shape[0]
+    if weights is None:
+        return values.mean(dim=0), values.std(dim=0, unbiased=True) / float(B) ** 0.5
+    if not isinstance(weights, torch.Tensor) or not weights.is_floating_point():
+        raise TypeError(f"{what}: weights is a floating tensor of {B} non-negative weights (the norms), not outcomes, records' integer "
+                        f"view or a selector; got {weights.dtype if isinstance(weights, torch.Tensor) else type(weights).__name__}")
+    if weights.dim() != 1 or weights.shape[0] != B or weights.device != values.device:
+        raise ValueError(f"{what}: weights has one entry per trajectory, shape [{B}] on {values.device}; got shape "
+                         f"{tuple(weights.shape)} on {weights.device}")
+    w = weights.to(values.dtype).reshape((B,) + (1,) * (values.dim() - 1))
+    live, zero = w != 0, torch.zeros((), dtype=values.dtype, device=values.device)
+    total = w.sum(dim=0)
+    mean = torch.where(live, w * values, zero).sum(dim=0) / total
+    err = torch.where(live, (w * (values - mean)) ** 2, zero).sum(dim=0).sqrt() / total
+    return mean, err

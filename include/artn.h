@@ -1279,6 +1279,70 @@ int artn_cgate_batch_apply(const ArtnMarginalDesc *d, void *a, int32_t t, const 
                            int64_t table_bytes, const void *selector, int64_t selector_stride, int64_t mask, void *stream);
 
 /*
+ * PAULI EXPECTATION VALUES PER TRAJECTORY: <psi_b|P|psi_b> of every state b of a batched tensor, one pass over the whole tensor
+ * for up to terms_per_launch strings of equal xmask (additive to ABI 9: has("artn_pauli_batch_expect")).  Descriptor, `ops`,
+ * global masks, groups and layout refusals are those of artn_pauli_query in the wording "batched Pauli expectations take ...";
+ * batch_dims are those of the batched trajectories above (every batch bit at or above a 128-byte line, at most
+ * ARTN_BATCH_MAX_BITS of them).  Strings carry I on every batch dimension.  The kernels only read the state.
+ *
+ * FORMULA.  The tensor has n = 2^L elements and a trajectory M = L - batch_bits LOCAL bits: local bit j is the j-th lowest memory
+ * bit that is no batch bit.  The LOCAL MASKS xl, zl are xmask, zmask compressed onto the local bits.  With a_b[l] the element of
+ * trajectory b at local index l,
+ *     out[b][t] = sum_l conj(a_b[l ^ xl]) * i^n_y * (-1)^popcount(l & zl) * a_b[l]      (real),   out[b][n_terms] = sum_l |a_b[l]|^2
+ * in the caller's term order.  Forms, signs and the summation order are functions of M, xl and zl alone: row b does not depend on
+ * where the batch bits lie in memory.
+ *
+ * PLAN.  M >= 10: a local tile is 2^10 consecutive local indices, T = 2^(M-10) of them per trajectory, T / 2 where xl >= 2^10 (the
+ * tiles whose highest xl bit is 0, weight 2).  A UNIT is (b, c), 0 <= c < C, C = min(T, max(1, 2048 >> batch_bits)) (`chunks`, and
+ * `chunks_halved` from T / 2): chunk c takes the local tiles c, c + C, ... in ascending order, thread t of the workgroup the local
+ * elements 4t .. 4t+3 of each, one fixed tree over the workgroup ends the unit, and a second launch adds the C partials of every
+ * (b, term) in ascending c and writes out.  M < 10: a workgroup takes 2^(10-M) whole trajectories, 2^(M-2) threads each, and the
+ * tree stops below the trajectory; C = 1.  Terms are those of artn_pauli_expect (float64 first, one rounding per Re q and Im q).
+ * No floating-point atomics: bit-identical from run to run.
+ *
+ * EXACTNESS.  nb == 0 is B = 1 and gives artn_pauli_expect's out bit for bit.  For B > 1, row b is bit for bit what
+ * artn_pauli_expect gives on a dense copy of trajectory b with its dimensions in local-bit order whenever M >= 10 and
+ * B * T <= 2048 (then C = T: every unit is one tile, as every workgroup of the unbatched pass); elsewhere the two differ by the
+ * summation order alone.  The norm comes from the call's first pass, as there.
+ *
+ * LIMITS.  B * (n_terms + 1) <= 2^28 (2 GiB of output).  workspace_bytes = B * chunks * 17 * 8.  Everything runs on `stream` with the
+ * caller's buffers: no allocation, copy or synchronisation.
+ *
+ * ARTN_E_INVALID: what artn_pauli_query calls invalid; X, Y or Z on a batch dimension; a batch dimension out of range or
+ * repeated; nb < 0; a workspace smaller than the query reports.  ARTN_E_UNSUPPORTED: a batch bit below the line; more than
+ * ARTN_BATCH_MAX_BITS batch bits; B * (n_terms + 1) above 2^28; `a` not 16-byte aligned, `out` or `ws` not 8-byte aligned; the
+ * refusals of artn_pauli_query.  ARTN_E_NODEVICE (artn_pauli_batch_expect, once every argument has passed): no device.
+ */
+typedef struct ArtnPauliBatchInfo {
+  int32_t n_groups;         /* distinct xmasks                                                       */
+  int32_t n_launches;       /* passes over the tensor; each is followed by one finish launch         */
+  int32_t terms_per_launch; /* strings one pass serves                                               */
+  int32_t batch_bits;       /* log2 B                                                                */
+  int32_t local_bits;       /* M                                                                     */
+  int32_t tile_bits;        /* min(10, M)                                                            */
+  int32_t n_fields;         /* batch fields after merging                                            */
+  int32_t grid;             /* workgroups of a pass with xl < 2^10                                   */
+  int64_t chunks;           /* C where xl < 2^10                                                     */
+  int64_t chunks_halved;    /* C where xl >= 2^10                                                    */
+  int64_t B, n;             /* trajectories; elements of the whole tensor                            */
+  int64_t workspace_bytes;
+  int64_t out_bytes;        /* B * (n_terms + 1) * 8                                                 */
+  int64_t bytes_read;       /* n_launches * bytes of the tensor                                      */
+  int32_t field_shift[ARTN_BATCH_MAX_FIELDS]; /* as ArtnBatchInfo's */
+  int32_t field_width[ARTN_BATCH_MAX_FIELDS];
+  int32_t field_pos[ARTN_BATCH_MAX_FIELDS];
+} ArtnPauliBatchInfo;
+/* Host-only: validates, translates every term to global and local masks, groups by xmask, splits the work, sizes the workspace.
+ * xmask, zmask, n_y, group, local_xmask, local_zmask: n_terms entries each, any of them may be NULL. */
+int artn_pauli_batch_query(const ArtnMarginalDesc *d, const uint8_t *ops, int64_t n_terms, int32_t nb, const int32_t *batch_dims,
+                           ArtnPauliBatchInfo *info, uint64_t *xmask, uint64_t *zmask, int32_t *n_y, int32_t *group,
+                           uint64_t *local_xmask, uint64_t *local_zmask);
+/* out (device, float64 [B][n_terms + 1]): row b holds the raw sums of trajectory b in the caller's term order, then its
+ * sum |a|^2.  ws: device, at least workspace_bytes. */
+int artn_pauli_batch_expect(const ArtnMarginalDesc *d, const void *a, const uint8_t *ops, int64_t n_terms, int32_t nb,
+                            const int32_t *batch_dims, double *out, void *ws, int64_t ws_bytes, void *stream);
+
+/*
  * DIAGONAL OPERATORS: a classical cost function f(i) = sum_k c_k (-1)^popcount(i & zmask_k) applied as ONE object, one streaming
  * pass per operation whatever the number of terms (additive to ABI 9: has("artn_diag_apply")).  Descriptor, `ops` (uint8
  * [n_terms][n_dims], I and Z only: codes 0 and 3), masks and layout refusals are those of artn_pauli_query in the wording
