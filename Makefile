@@ -6,13 +6,13 @@ LIB := artensor_amd/libartn_hip.so
 
 all: $(LIB)
 
-# Twenty-seven objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit), one
+# Twenty-eight objects, one per source: the main unit artn_api.hip (dispatch, C ABI, every kernel the others do not emit), one
 # artn_<family>.hip per word of FAMILIES, and the eleven few-line sources under units/, each of which defines one
 # artn_launch_*() and so emits one family of the state-streaming kernels of artn_kernels.hip (device code only, included by
 # all of them).  `make -j8` builds in about a minute and a half instead of four.  What an object depends on beyond its source
 # is what the compiler saw it include (-MMD -MP: build/obj/<object>.d, read back below); no list of headers is kept by hand.
 # A new family is one word here and one #include in artn_unity.hip.
-FAMILIES := born rdm pauli gates wgate mgate cgate krylov measure channel batch cgate_batch pauli_batch diag bitperm
+FAMILIES := born rdm pauli gates wgate mgate cgate krylov measure channel batch cgate_batch pauli_batch sample_batch diag bitperm
 # (the single-translation-unit builds below: artn_unity.hip includes every unit source)
 SRCS := $(CSRC)/artn_unity.hip $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/units/*.hip) include/artn.h
 OBJDIR := build/obj

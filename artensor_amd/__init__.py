@@ -178,6 +178,9 @@ from .trajectories import (  # noqa: F401
     pauli_sum_expectation_batch,
     postselect_batch_,
     reset_batch_,
+    sample_batch,
+    sample_batch_flat,
+    sample_batch_info,
     trajectory_info,
     trajectory_mean,
     trajectory_norms,

@@ -370,6 +370,30 @@ class ArtnPauliBatchInfo(ctypes.Structure):
     ]
 
 
+SAMPLE_BATCH_SMALL, SAMPLE_BATCH_TILED = 0, 1
+
+
+class ArtnSampleBatchInfo(ctypes.Structure):
+    _fields_ = [
+        ("form", ctypes.c_int32),
+        ("launches", ctypes.c_int32),
+        ("batch_bits", ctypes.c_int32),
+        ("local_bits", ctypes.c_int32),
+        ("block_bits", ctypes.c_int32),
+        ("n_fields", ctypes.c_int32),
+        ("grid", ctypes.c_int32 * 3),
+        ("reserved", ctypes.c_int32),
+        ("B", ctypes.c_int64),
+        ("n", ctypes.c_int64),
+        ("blocks_per_trajectory", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("bytes_read_min", ctypes.c_int64),
+        ("field_shift", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_width", ctypes.c_int32 * BATCH_MAX_FIELDS),
+        ("field_pos", ctypes.c_int32 * BATCH_MAX_FIELDS),
+    ]
+
+
 DIAG_MAX_GROUPS, DIAG_MAX_TERMS, DIAG_TILE_BITS = 64, 65536, 10
 DIAG_PHASE, DIAG_MULTIPLY = 0, 1
 DIAG_PAIR_EVOLVE, DIAG_PAIR_TRANSITION = 0, 1
@@ -614,6 +638,12 @@ _EXPORTS = {
     "artn_pauli_batch_expect": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_void_p]),
+    # additive to ABI 9 as well: bitstring sampling per trajectory of a batched tensor (has("artn_sample_batch"))
+    "artn_sample_batch_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.POINTER(ArtnSampleBatchInfo)]),
+    "artn_sample_batch": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     # additive to ABI 9 as well: diagonal operators -- cost-function phases, moments and pairs in one pass (has("artn_diag_apply"))
     "artn_diag_query": (ctypes.c_int, [ctypes.POINTER(ArtnMarginalDesc), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.POINTER(ArtnDiagInfo), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

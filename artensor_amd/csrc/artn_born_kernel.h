@@ -161,24 +161,35 @@ static __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_finish(c
 #define BORN_PIDX(s) ((s) + ((s) >> 4))
 #define BORN_PSEG_DOUBLES (ARTN_BORN_MAX_SEGS + (ARTN_BORN_MAX_SEGS >> 4))
 
-// Inclusive prefix sums of the 4-element segment sums of the block [base, base + 2^bbits) into pseg[BORN_PIDX(s)], elements at or
-// beyond n counting as zero.  Segment sum = ((t0 + t1) + t2) + t3; prefix as described at the top of this file.
-template <typename T>
-__device__ __forceinline__ void born_block_scan(const T *__restrict__ a, long n, long base, int bbits, double *pseg, double *tot) {
+// Where the segments of a block lie.  tile(q, tid): the first element of segment q * ARTN_BORN_THREADS + tid, as the scan walks
+// them; seg(s): of segment s, wherever a pick lands.  BornSegLinear is a block of consecutive memory elements;
+// artn_sample_batch_kernel.h has the one of a trajectory whose local bits are spread over memory.
+struct BornSegLinear {
+  long base;
+  __device__ __forceinline__ long tile(int q, int tid) const { return base + ((long)(q * ARTN_BORN_THREADS + tid)) * 4; }
+  __device__ __forceinline__ long seg(int s) const { return base + (long)s * 4; }
+};
+
+// Inclusive prefix sums of the 4-element segment sums of a block of 2^bbits elements into pseg[BORN_PIDX(s)]; `whole` (uniform):
+// every element of the block exists, otherwise those whose address is at or beyond n count as zero.  Segment sum =
+// ((t0 + t1) + t2) + t3; prefix as described at the top of this file.
+template <typename T, typename AT>
+__device__ __forceinline__ void born_block_scan_at(const T *__restrict__ a, long n, bool whole, const AT &at, int bbits, double *pseg,
+                                                   double *tot) {
   const int tid = threadIdx.x;
   const int S = 1 << (bbits - 2), K = S / ARTN_BORN_THREADS; // bbits >= 10: K >= 1
-  if (base + ((long)1 << bbits) <= n) {
+  if (whole) {
 #pragma unroll 4
-    for (int s = tid; s < S; s += ARTN_BORN_THREADS) {
+    for (int q = 0; q < K; ++q) {
       double t[4];
-      born_seg4(a, base + (long)s * 4, t);
-      pseg[BORN_PIDX(s)] = ((t[0] + t[1]) + t[2]) + t[3];
+      born_seg4(a, at.tile(q, tid), t);
+      pseg[BORN_PIDX(q * ARTN_BORN_THREADS + tid)] = ((t[0] + t[1]) + t[2]) + t[3];
     }
   } else {
-    for (int s = tid; s < S; s += ARTN_BORN_THREADS) {
+    for (int q = 0; q < K; ++q) {
       double t[4];
-      born_seg4_tail(a, base + (long)s * 4, n, t);
-      pseg[BORN_PIDX(s)] = ((t[0] + t[1]) + t[2]) + t[3];
+      born_seg4_tail(a, at.tile(q, tid), n, t);
+      pseg[BORN_PIDX(q * ARTN_BORN_THREADS + tid)] = ((t[0] + t[1]) + t[2]) + t[3];
     }
   }
   __syncthreads();
@@ -208,6 +219,11 @@ __device__ __forceinline__ void born_block_scan(const T *__restrict__ a, long n,
     }
   __syncthreads();
 }
+// the block [base, base + 2^bbits) of consecutive elements
+template <typename T>
+__device__ __forceinline__ void born_block_scan(const T *__restrict__ a, long n, long base, int bbits, double *pseg, double *tot) {
+  born_block_scan_at(a, n, base + ((long)1 << bbits) <= n, BornSegLinear{base}, bbits, pseg, tot);
+}
 
 template <typename T>
 __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_block_sums(const T *__restrict__ a, long n, int bbits,
@@ -218,9 +234,8 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_block_sums(cons
   if (threadIdx.x == 0) block_sum[blockIdx.x] = pseg[BORN_PIDX((1 << (bbits - 2)) - 1)];
 }
 
-static __global__ __launch_bounds__(ARTN_BORN_PREFIX_THREADS) void artn_k_born_prefix(const double *__restrict__ block_sum,
-                                                                               double *__restrict__ prefix, long nb) {
-  __shared__ double tot[ARTN_BORN_PREFIX_THREADS];
+// the body of artn_k_born_prefix: one workgroup of ARTN_BORN_PREFIX_THREADS threads, one row of nb sums (tot: LDS, one per thread)
+__device__ __forceinline__ void born_prefix_row(const double *__restrict__ block_sum, double *__restrict__ prefix, long nb, double *tot) {
   const int tid = threadIdx.x;
   const long K = (nb + ARTN_BORN_PREFIX_THREADS - 1) / ARTN_BORN_PREFIX_THREADS;
   const long lo = tid * K < nb ? tid * K : nb, hi = lo + K < nb ? lo + K : nb;
@@ -246,15 +261,55 @@ static __global__ __launch_bounds__(ARTN_BORN_PREFIX_THREADS) void artn_k_born_p
   if (tid > 0)
     for (long i = lo; i < hi; ++i) prefix[i] = b + prefix[i]; // (each thread re-reads its own stores only)
 }
+static __global__ __launch_bounds__(ARTN_BORN_PREFIX_THREADS) void artn_k_born_prefix(const double *__restrict__ block_sum,
+                                                                               double *__restrict__ prefix, long nb) {
+  __shared__ double tot[ARTN_BORN_PREFIX_THREADS];
+  born_prefix_row(block_sum, prefix, nb, tot);
+}
 
-__device__ __forceinline__ long born_lower_bound(const double *__restrict__ x, long m, double v) { // first s with x[s] >= v
+template <typename X> __device__ __forceinline__ long born_lower_bound_of(const X &x, long m, double v) { // first s with x(s) >= v
   long lo = 0, hi = m;
   while (lo < hi) {
     const long mid = (lo + hi) >> 1;
-    if (x[mid] >= v) hi = mid;
+    if (x(mid) >= v) hi = mid;
     else lo = mid + 1;
   }
   return lo;
+}
+__device__ __forceinline__ long born_lower_bound(const double *__restrict__ x, long m, double v) { // first s with x[s] >= v
+  return born_lower_bound_of([&](long s) { return x[s]; }, m, v);
+}
+
+// One target of a scanned block: r = target - (what lies before the block), ptot the block's own total.  The block's S segments
+// are pseg[BORN_PIDX(s0 .. s0 + S - 1)] (entries after the last non-zero segment equal ptot).  The smallest element whose running
+// sum exceeds r, never one with |a|^2 == 0; r at or past ptot: the last non-zero element.  *index is the element's address.
+template <typename T, typename AT>
+__device__ __forceinline__ void born_pick_one(const T *__restrict__ a, long n, const AT &at, int s0, int S, const double *pseg, double ptot,
+                                              double r, long long *__restrict__ index, double *__restrict__ prob) {
+  const bool beyond = !(ptot > r); // at or past the block's own total: the last non-zero element
+  int lo = 0, hi = S - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const double p = pseg[BORN_PIDX(s0 + mid)];
+    if (beyond ? (p >= ptot) : (p > r)) hi = mid;
+    else lo = mid + 1;
+  }
+  double t[4];
+  const long i0 = at.seg(lo);
+  born_seg4_tail(a, i0, n, t);
+  double run = lo ? pseg[BORN_PIDX(s0 + lo - 1)] : 0.0;
+  int pick = -1, lastnz = -1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    run += t[e];
+    if (t[e] > 0.0) {
+      lastnz = e;
+      if (pick < 0 && !beyond && run > r) pick = e;
+    }
+  }
+  if (pick < 0) pick = lastnz;
+  *index = pick < 0 ? -1 : (long long)(i0 + pick);
+  *prob = pick == 0 ? t[0] : pick == 1 ? t[1] : pick == 2 ? t[2] : pick == 3 ? t[3] : 0.0;
 }
 
 // Workgroup j resolves the targets t with prefix[j-1] <= t < prefix[j] (the last block whose prefix grew also takes every t at or
@@ -278,33 +333,8 @@ __global__ __launch_bounds__(ARTN_BORN_THREADS) void artn_k_born_pick(const T *_
   born_block_scan(a, n, base, bbits, pseg, tot);
   const int S = 1 << (bbits - 2);
   const double ptot = pseg[BORN_PIDX(S - 1)];
-  for (long s = s_lo + threadIdx.x; s < s_hi; s += ARTN_BORN_THREADS) {
-    double r = targets[s] - lo_t;
-    const bool beyond = !(ptot > r); // at or past the block's own total: the last non-zero element
-    int lo = 0, hi = S - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      const double p = pseg[BORN_PIDX(mid)];
-      if (beyond ? (p >= ptot) : (p > r)) hi = mid;
-      else lo = mid + 1;
-    }
-    double t[4];
-    const long i0 = base + (long)lo * 4;
-    born_seg4_tail(a, i0, n, t);
-    double run = lo ? pseg[BORN_PIDX(lo - 1)] : 0.0;
-    int pick = -1, lastnz = -1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      run += t[e];
-      if (t[e] > 0.0) {
-        lastnz = e;
-        if (pick < 0 && !beyond && run > r) pick = e;
-      }
-    }
-    if (pick < 0) pick = lastnz;
-    out_index[s] = pick < 0 ? -1 : (long long)(i0 + pick);
-    out_prob[s] = pick == 0 ? t[0] : pick == 1 ? t[1] : pick == 2 ? t[2] : pick == 3 ? t[3] : 0.0;
-  }
+  for (long s = s_lo + threadIdx.x; s < s_hi; s += ARTN_BORN_THREADS)
+    born_pick_one(a, n, BornSegLinear{base}, 0, S, pseg, ptot, targets[s] - lo_t, out_index + s, out_prob + s);
 }
 
 // ---- marginals -----------------------------------------------------------------------------------------------------

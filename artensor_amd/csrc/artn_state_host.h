@@ -1,6 +1,6 @@
 // artn_state_host.h -- host plumbing shared by the operations on a dense amplitude array (artn_born.hip, artn_rdm.hip,
 // artn_pauli.hip, artn_gates.hip, artn_wgate.hip, artn_mgate.hip, artn_cgate.hip, artn_measure.hip, artn_channel.hip,
-// artn_batch.hip, artn_cgate_batch.hip, artn_pauli_batch.hip, artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the batch dimensions, the max_rank rule and the rank dispatch of the run
+// artn_batch.hip, artn_cgate_batch.hip, artn_pauli_batch.hip, artn_sample_batch.hip, artn_diag.hip, artn_bitperm.hip): the descriptor and layout checks, the batch dimensions, the max_rank rule and the rank dispatch of the run
 // kernels, the matrix scan, the argument checks of the pack / apply entries, the parts of a packed table, the plan, the
 // column packer, the table header and the K dispatch of the tile kernels (wide gates, matrix gates, controlled gates,
 // channels).  The whole host half of the two dense-gate families is artn_dense_gate_host.h, what the four run-circuit

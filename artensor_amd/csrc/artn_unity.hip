@@ -31,5 +31,6 @@
 #include "artn_batch.hip" // (artn_batch_kernel.h)
 #include "artn_cgate_batch.hip" // (artn_cgate_batch_kernel.h)
 #include "artn_pauli_batch.hip" // (artn_pauli_batch_kernel.h)
+#include "artn_sample_batch.hip" // (artn_sample_batch_kernel.h)
 #include "artn_diag.hip" // (artn_diag_kernel.h)
 #include "artn_bitperm.hip" // (artn_bitperm_kernel.h)

@@ -21,6 +21,8 @@ they are.  Here every trajectory gets its own outcome or Kraus operator:
     pauli_expectation_batch  <psi_b|P|psi_b> of every trajectory for up to sixteen strings of equal X/Y positions per pass over the
                        tensor (C ABI: artn_pauli_batch_query / _expect); pauli_sum_expectation_batch is sum_k c_k <P_k> per
                        trajectory, trajectory_mean the (weighted) mean over trajectories and its standard error
+    sample_batch       S bitstrings from every trajectory, drawn from |amps_b|^2 / norm_b with uniforms[b, :] (C ABI:
+                       artn_sample_batch_query / artn_sample_batch); sample_batch_flat returns flat memory indices and the norms
 
 Slice b afterwards is bit for bit what the unbatched call leaves on that slice with record[b]: measure.collapse_ for the
 measurements, apply_wide_gate_(slice, K_j * scale) for the channels.  A trajectory where nothing can be observed or drawn
@@ -42,7 +44,7 @@ import torch
 
 from . import _native
 from ._state import _Prebuilt, _checked, _dense_layout, _desc, _dims, _dtype_code, _interleaved, _lib, _packed, _ptr
-from .born import marginal_probabilities
+from .born import marginal_probabilities, memory_to_multi_index
 from .channel import Channel, _split
 from .controlled import _split_dims
 from .gates import _matrix
@@ -51,7 +53,8 @@ from .pauli import pauli_ops
 
 __all__ = ["measure_batch_", "postselect_batch_", "reset_batch_", "collapse_batch_", "BatchChannelOp", "channel_batch_",
            "trajectory_info", "trajectory_norms", "BatchConditionalGate", "apply_conditional_gate_batch_", "conditional_gate_info",
-           "correct_batch_", "pauli_expectation_batch", "pauli_sum_expectation_batch", "trajectory_mean", "pauli_batch_info"]
+           "correct_batch_", "pauli_expectation_batch", "pauli_sum_expectation_batch", "trajectory_mean", "pauli_batch_info",
+           "sample_batch", "sample_batch_flat", "sample_batch_info"]
 
 _KERNELS = ("artn_channel_batch_apply", "batched-trajectory kernels")   # what _lib looks for, and what it calls them
 _LINE_BIT = {torch.complex64: 4, torch.complex128: 3}                   # index bits of a 128-byte line
@@ -551,3 +554,109 @@ def trajectory_mean(values, weights=None):
     mean = torch.where(live, w * values, zero).sum(dim=0) / total
     err = torch.where(live, (w * (values - mean)) ** 2, zero).sum(dim=0).sqrt() / total
     return mean, err
+
+
+# ---- bitstrings per trajectory ------------------------------------------------------------------------------------------------------
+_SAMPLE_KERNELS = ("artn_sample_batch", "batched sampling kernels")
+_SAMPLE_FORMS = {_native.SAMPLE_BATCH_SMALL: "SMALL", _native.SAMPLE_BATCH_TILED: "TILED"}
+
+
+def _sample_plan(shape, strides, batch_dims, n_samples, dtype, what):
+    """(descriptor, batch dims, info).  The family's refusals by name (_batch), then the library's (n > 2^40, B * S > 2^28)."""
+    batch, B = _batch(shape, strides, (), batch_dims, dtype, "sampled", what)
+    n, S = _dense_layout(shape, strides), int(n_samples)
+    if S < 0:
+        raise ValueError(f"{what}: n_samples must not be negative, got {S}")
+    if n > 2 ** 40:
+        raise ValueError(f"{what}: at most 2^40 elements, this tensor has {n}")
+    if B * S > 2 ** 28:
+        raise ValueError(f"{what}: B * n_samples = {B} * {S} is above 2^28 samples (2 GiB of indices)")
+    d, info = _desc(shape, strides, dtype), _native.ArtnSampleBatchInfo()
+    _native.check(_lib(*_SAMPLE_KERNELS, what).artn_sample_batch_query(ctypes.byref(d), batch.shape[0],
+                                                                       _ptr(batch) if batch.shape[0] else None, S, ctypes.byref(info)))
+    return d, batch, info
+
+
+def sample_batch_info(shape, strides, batch_dims, n_samples, dtype=torch.complex64):
+    """Host-only: the plan of sample_batch.  B, n, batch_bits, local_bits (M), block_bits and blocks_per_trajectory (those of
+    born_plan(2^M)), form ("SMALL": M < 10 and B > 1, one launch; "TILED": three), fields (as trajectory_info's), launches, grid
+    (the workgroups of each launch), workspace_bytes (B * blocks_per_trajectory * 16; 0 for SMALL) and bytes_read_min (one
+    reading of the tensor)."""
+    _, _, info = _sample_plan(shape, strides, batch_dims, n_samples, dtype, "sample_batch_info")
+    return {"B": info.B, "n": info.n, "batch_bits": info.batch_bits, "local_bits": info.local_bits, "block_bits": info.block_bits,
+            "blocks_per_trajectory": info.blocks_per_trajectory, "form": _SAMPLE_FORMS[info.form],
+            "fields": [(int(info.field_shift[f]), int(info.field_width[f]), int(info.field_pos[f])) for f in range(info.n_fields)],
+            "launches": info.launches, "grid": [int(g) for g in info.grid[:info.launches]], "workspace_bytes": info.workspace_bytes,
+            "bytes_read_min": info.bytes_read_min}
+
+
+def _sample_uniforms(uniforms, n_samples, generator, B, device, what):
+    """float64 [B, S] on `device`.  Host-only checks: dtype and shape; the values are never read here."""
+    if uniforms is None:
+        if n_samples is None or int(n_samples) < 0:
+            raise ValueError(f"{what}: give n_samples or uniforms")
+        return None, int(n_samples)
+    if not isinstance(uniforms, torch.Tensor) or uniforms.dtype != torch.float64:
+        raise ValueError(f"{what}: uniforms is a float64 GPU tensor [B, S] = [{B}, n_samples], one row per trajectory")
+    if uniforms.dim() != 2 or uniforms.shape[0] != B:
+        raise ValueError(f"{what}: uniforms has shape [B, S] = [{B}, n_samples], one row per trajectory; got {tuple(uniforms.shape)}")
+    if n_samples is not None and int(n_samples) != uniforms.shape[1]:
+        raise ValueError(f"{what}: n_samples = {int(n_samples)} disagrees with uniforms of shape {tuple(uniforms.shape)}")
+    if not uniforms.is_cuda or uniforms.device != device:
+        raise ValueError(f"{what}: uniforms must live on {device}, where the amplitudes are; got {uniforms.device}")
+    return uniforms, int(uniforms.shape[1])
+
+
+def sample_batch_flat(amps, batch_dims, n_samples=None, *, uniforms=None, generator=None):
+    """S draws from every trajectory.  Returns (flat, prob, norms) on the device: flat int64 [B, S], the flat MEMORY index of
+    sample (b, s) in the whole tensor (what born.memory_to_multi_index takes); prob float64 [B, S] = |amps[flat]|^2 / norms[b];
+    norms float64 [B] = sum |amps_b|^2.  See sample_batch for the arguments and the rule.  With S = 0 nothing is launched and
+    norms is NaN: it was not computed."""
+    what = "trajectories.sample_batch_flat"
+    _checked(amps, what)
+    dev = amps.device
+    B = _batch(amps.shape, amps.stride(), (), batch_dims, amps.dtype, "sampled", what)[1]
+    uniforms, S = _sample_uniforms(uniforms, n_samples, generator, B, dev, what)
+    d, batch, info = _sample_plan(amps.shape, amps.stride(), batch_dims, S, amps.dtype, what)
+    if S == 0:
+        return (torch.empty((B, 0), dtype=torch.int64, device=dev), torch.empty((B, 0), dtype=torch.float64, device=dev),
+                torch.full((B,), float("nan"), dtype=torch.float64, device=dev))
+    if uniforms is None:
+        uniforms = torch.rand((B, S), dtype=torch.float64, device=dev, generator=generator)
+    us, order = torch.sort(uniforms.contiguous(), dim=1)  # ascending per row: a block is read once for all its samples
+    us = us.contiguous()                                  # (the library reads rows of S consecutive doubles)
+    flat_sorted = torch.empty((B, S), dtype=torch.int64, device=dev)
+    prob_sorted = torch.empty((B, S), dtype=torch.float64, device=dev)
+    norms = torch.empty(B, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(info.workspace_bytes // 8, 1), dtype=torch.float64, device=dev)   # (per call: calls may overlap on streams)
+    with torch.cuda.device(dev):
+        _native.check(_lib(*_SAMPLE_KERNELS, what).artn_sample_batch(
+            ctypes.byref(d), amps.data_ptr(), batch.shape[0], _ptr(batch) if batch.shape[0] else None, us.data_ptr(), S,
+            flat_sorted.data_ptr(), prob_sorted.data_ptr(), norms.data_ptr(), ws.data_ptr(), info.workspace_bytes,
+            _native.current_stream_ptr(dev)))
+    live = (torch.isfinite(norms) & (norms > 0))[:, None]
+    flat = torch.empty_like(flat_sorted).scatter_(1, order, flat_sorted)
+    prob = torch.empty_like(prob_sorted).scatter_(1, order, prob_sorted / norms[:, None])
+    flat = torch.where(live, flat, torch.full_like(flat, -1))
+    prob = torch.where(live, prob, torch.full_like(prob, float("nan")))
+    return flat, prob, norms
+
+
+def sample_batch(amps, batch_dims, n_samples=None, *, uniforms=None, generator=None):
+    """Draw S multi-indices from EVERY trajectory of amps with probability |amps_b[idx]|^2 / norm_b.
+
+    Returns (idx, prob) on the device: idx int64 [B, S, amps.dim()], multi-indices in the tensor's logical dim order, the batch
+    dims' columns holding the digits of b; prob float64 [B, S].  `uniforms` is a float64 GPU tensor [B, S], any order within a
+    row; sample (b, s) belongs to uniforms[b, s]: it is the element of trajectory b whose cumulative-probability interval, in
+    LOCAL-index order (local bit j: the j-th lowest memory bit that is no batch bit), contains uniforms[b, s].  Without
+    `uniforms`, torch.rand((B, n_samples), dtype=float64, generator=generator) on the device supplies them.  Only dtype and shape
+    of `uniforms` are checked (on the host: the values are never read there); a value at or above 1 takes the trajectory's last
+    non-zero element, a negative one gives index -1 and probability 0.
+
+    Row b is bit for bit what born.sample gives on a dense clone of slice b with its dims in local-bit order and uniforms[b];
+    batch_dims=() is born.sample itself, without its host synchronisation.  A DEAD trajectory (its norm 0 or not finite) is no
+    error: its rows are -1 in every column of idx and NaN in prob, and it changes no other row.  The call only enqueues on the
+    current stream and can be captured into a HIP graph.  Limits: power-of-two extents, n <= 2^40, B * S <= 2^28."""
+    flat, prob, _ = sample_batch_flat(amps, batch_dims, n_samples, uniforms=uniforms, generator=generator)
+    idx = memory_to_multi_index(flat, amps.shape, amps.stride())
+    return torch.where((flat < 0)[..., None], torch.full_like(idx, -1), idx), prob

@@ -1343,6 +1343,75 @@ int artn_pauli_batch_expect(const ArtnMarginalDesc *d, const void *a, const uint
                             const int32_t *batch_dims, double *out, void *ws, int64_t ws_bytes, void *stream);
 
 /*
+ * BITSTRING SAMPLING PER TRAJECTORY: S draws from every state b of a batched tensor, B cumulative distributions in one tensor
+ * (additive to ABI 9: has("artn_sample_batch")).  It generalises artn_born_block_sums + artn_born_pick above, which draw from
+ * ONE array, to the trajectories of BATCHED TRAJECTORIES: the descriptor and the layout refusals are those of the families
+ * that index the state by bits, in the wording "batched sampling takes ..."; batch_dims are those of the batched trajectories
+ * (every batch bit at or above a 128-byte line, at most ARTN_BATCH_MAX_BITS of them; nb == 0 is B = 1).  The state is only read.
+ *
+ * CONTRACT.  The tensor has n = 2^L elements and a trajectory M = L - batch_bits LOCAL bits: local bit j is the j-th lowest
+ * memory bit that is no batch bit (as for artn_pauli_batch_expect).  The cumulative distribution of trajectory b runs over its
+ * 2^M elements IN LOCAL-INDEX ORDER, with exactly the arithmetic of the unbatched entries on an array of 2^M elements: terms
+ * |a|^2 formed in float64 with one rounding, 4-element segment sums ((t0 + t1) + t2) + t3, the in-block prefix of
+ * artn_born_block_sums, blocks of artn_born_plan(2^M).block_bits bits, the prefix over the nb_t = blocks_per_trajectory block
+ * sums that artn_born_block_sums forms for n_blocks = nb_t (a function of nb_t alone; for nb_t <= 1024 the plain ascending
+ * running sum).  norm_b is the last prefix entry.  The target of (b, s) is the single multiply uniforms[b][s] * norm_b, and
+ * the pick is artn_born_pick's: the smallest local index whose running sum exceeds the target, never an element with
+ * |a|^2 == 0, a target at or beyond norm_b the last non-zero element.  A uniform outside [0, 1) is not refused: one at or
+ * above 1 takes the last non-zero element, a negative one yields index -1 and probability 0.
+ *   Hence row b of the outputs is, bit for bit, what artn_born_block_sums + artn_born_pick give on a dense copy of trajectory b
+ * with its dimensions in local-bit order and targets = uniforms[b] * norm_b -- its index deposited into the memory bits that
+ * are no batch bits, OR'd with b deposited into the fields; nb == 0 gives those entries' results themselves.  A row depends
+ * neither on where the batch bits lie nor on the other rows.  No floating-point atomics: bit-identical from run to run.
+ *
+ * FORMS.  ARTN_SAMPLE_BATCH_TILED (M >= 10, or B == 1), three launches: block sums, a unit being (b, block j), workgroups
+ * looping over units above 2^20 of them; the prefix per trajectory, which also writes out_norm (one 1024-thread workgroup per
+ * trajectory where nb_t > 1024, else 1024 / nb_t rows per workgroup); the pick, a unit being (b, j) again: it bisects row b of
+ * the uniforms, on the products, for the targets of its block and leaves before touching the amplitudes when it has none.
+ * ARTN_SAMPLE_BATCH_SMALL (M < 10 and B > 1), ONE launch: a workgroup takes 2^(10-M) whole trajectories, 2^(M-2) threads
+ * each.  The uniforms are sorted, not the targets (multiplying by a positive norm is monotone), so the entry needs nothing
+ * that depends on the state.
+ *
+ * LIMITS.  n <= 2^40; B * n_samples <= 2^28; `a` 16-byte aligned, everything else 8-byte aligned.  workspace_bytes =
+ * B * nb_t * 2 * 8 (block sums, then prefix; 0 for SMALL).  Everything runs on `stream` with the caller's buffers: no
+ * allocation, copy or synchronisation.  n_samples == 0 succeeds without a launch (out_norm is not written).
+ *
+ * ARTN_E_INVALID: a malformed descriptor or a tensor that is not dense; a batch dimension out of range or repeated; nb < 0;
+ * n_samples < 0; a null pointer; a workspace smaller than the query reports.  ARTN_E_UNSUPPORTED: a dtype other than
+ * complex64 / complex128; an extent that is no power of two; more than 2^40 elements; a batch bit below the line; more than
+ * ARTN_BATCH_MAX_BITS batch bits; B * n_samples above 2^28; a misaligned pointer.  ARTN_E_NODEVICE (artn_sample_batch, once
+ * every argument has passed): no device.
+ */
+#define ARTN_SAMPLE_BATCH_SMALL 0
+#define ARTN_SAMPLE_BATCH_TILED 1
+typedef struct ArtnSampleBatchInfo {
+  int32_t form;                  /* ARTN_SAMPLE_BATCH_*                                                   */
+  int32_t launches;              /* 1 (SMALL) or 3 (TILED); two memsets preset the outputs on top         */
+  int32_t batch_bits;            /* log2 B                                                                */
+  int32_t local_bits;            /* M                                                                     */
+  int32_t block_bits;            /* artn_born_plan(2^M).block_bits                                        */
+  int32_t n_fields;              /* batch fields after merging                                            */
+  int32_t grid[3];               /* workgroups of the launches (TILED: block sums, prefix, pick)          */
+  int32_t reserved;
+  int64_t B, n;                  /* trajectories; elements of the whole tensor                            */
+  int64_t blocks_per_trajectory; /* nb_t = artn_born_plan(2^M).n_blocks                                   */
+  int64_t workspace_bytes;
+  int64_t bytes_read_min;        /* one reading of the tensor (the pick re-reads the blocks with targets) */
+  int32_t field_shift[ARTN_BATCH_MAX_FIELDS]; /* as ArtnBatchInfo's */
+  int32_t field_width[ARTN_BATCH_MAX_FIELDS];
+  int32_t field_pos[ARTN_BATCH_MAX_FIELDS];
+} ArtnSampleBatchInfo;
+/* Host-only: validates, splits the work, sizes the workspace. */
+int artn_sample_batch_query(const ArtnMarginalDesc *d, int32_t nb, const int32_t *batch_dims, int64_t n_samples,
+                            ArtnSampleBatchInfo *info);
+/* uniforms_sorted (device, float64 [B][n_samples], ASCENDING per row).  out_index (device, int64 [B][n_samples]): the MEMORY
+ * index of the drawn element, -1 where nothing can be drawn; out_prob: its raw |a|^2; out_norm (device, float64 [B]): norm_b.
+ * ws: device, at least workspace_bytes (may be NULL when that is 0). */
+int artn_sample_batch(const ArtnMarginalDesc *d, const void *a, int32_t nb, const int32_t *batch_dims, const double *uniforms_sorted,
+                      int64_t n_samples, int64_t *out_index, double *out_prob, double *out_norm, void *ws, int64_t ws_bytes,
+                      void *stream);
+
+/*
  * DIAGONAL OPERATORS: a classical cost function f(i) = sum_k c_k (-1)^popcount(i & zmask_k) applied as ONE object, one streaming
  * pass per operation whatever the number of terms (additive to ABI 9: has("artn_diag_apply")).  Descriptor, `ops` (uint8
  * [n_terms][n_dims], I and Z only: codes 0 and 3), masks and layout refusals are those of artn_pauli_query in the wording
